@@ -8,20 +8,28 @@ holds 8192 streams). The streams are independent units, so there is no data-path
 One step is the reference's full round trip on the shard: `-c -m` encode (diff -> MNP-5 RLE ->
 FGK -> header, one fused kernel) then decode (FGK -> RLE revert -> diff revert, one fused kernel).
 value = raw bytes of all ranks / step time (max over ranks), GiB/s. After the timed region: every
-status 0, decode == input on every stream, and (rank 0, N=1) the first streams' encodings
-byte-identical to the reference binary's own output for them.
+status 0, decode == input on every stream.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only that: it sets the batch up, runs W warm-up and K timed steps (ms_per_step
+is the wall time of one of the K), checks the round trip, and prints the one JSON result line.
+`--dump-outputs DIR` also writes what the last timed step computed to DIR/<name>.npy (see
+dump_outputs: every stream's status, length and checksum, and a fixed sample of whole streams,
+encoded and decoded; the inputs are the same at every run of the same arguments, so two builds
+can be compared file for file). Everything below that takes runs of its own needs `--full`.
 
 `--gpus N` with N > 1 and no launcher around the process starts the N ranks itself (fresh child
 processes through torch.distributed.run, before anything here touches a GPU) and exits with their
-status; under a launcher, --gpus must equal WORLD_SIZE. At N > 1 the line also carries
-`weak_scaling`: every rank then codes a whole 65536-stream batch of its own (per-GPU work fixed),
-measured after the headline and reported beside it, never as `value`. `--weak` makes --streams a
-per-GPU count for the headline itself.
+status; under a launcher, --gpus must equal WORLD_SIZE. `--weak` makes --streams a per-GPU count
+for the headline itself.
 
-At N=1 the same JSON line also carries "configs": the other BASELINE.json configs measured in
+`--full` adds, after the headline and in the same JSON line: (N=1) `cpu_baseline`, the reference
+binary on the host CPUs on the first streams of the batch, whose outputs must equal the GPU's
+encodings of them byte for byte, and `roofline.measured_copy_GBps`; (N > 1) `weak_scaling`: every
+rank then codes a whole 65536-stream batch of its own (per-GPU work fixed), reported beside
+`value`, never as it; and (N=1) "configs": the other BASELINE.json configs measured in
 the same run (C1 the per-file CLI, C2 one stream, C3 4096 streams `-c`, C4 the 4096x4096
 adaptive matrix, the grad / noise distributions of SURVEY.md §8d, and C5_split2/4/8: the shard
 one GPU holds when C5 is split over 2 / 4 / 8 GPUs, with its efficiency against the whole batch),
@@ -61,19 +69,24 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the reference binary on the host CPUs, the measured HBM copy rate, "
+                         "the other BASELINE configs (N=1) and the weak-scaling line (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the last step computed to DIR/<name>.npy")
     ap.add_argument("--streams", "--total-streams", dest="streams", type=int, default=C5_STREAMS,
                     help="streams in the whole batch, split over the ranks (strong scaling; 65536 = C5)")
     ap.add_argument("--weak", action="store_true", help="--streams per GPU instead (weak scaling)")
     ap.add_argument("--no-weak-line", action="store_true",
-                    help="N > 1: skip the extra weak-scaling measurement (a whole C5 batch per GPU)")
+                    help="--full, N > 1: skip the extra weak-scaling measurement (a whole C5 batch per GPU)")
     ap.add_argument("--kind", default="photo", choices=["photo", "grad", "noise"])
     ap.add_argument("--no-diff", action="store_true", help="-c instead of -c -m")
     ap.add_argument("--cpu-sample", type=int, default=0, help="streams for the CPU baseline (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the reference binary on the host CPUs")
     ap.add_argument("--gather", action="store_true",
                     help="after the timed region: pack every rank's encoded shard on its GPU and send it to rank 0 "
                          "(the north star's final gather), timed and reported separately")
-    ap.add_argument("--no-configs", action="store_true", help="N=1: skip the other BASELINE configs")
+    ap.add_argument("--no-configs", action="store_true", help="--full, N=1: skip the other BASELINE configs")
     ap.add_argument("--only-configs", default="", help="comma list: run just these configs (no headline)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL on ROCm): the GPU run; gloo: a CPU dry run of the multi-rank path "
@@ -805,6 +818,65 @@ def workload_name(total, world, S, kind, use_diff, weak):
     return (f"{'C5: ' if c5 else ''}{total} x 512x512 {kind} streams ({how}), {mode} encode + decode round trip")
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: every file of every rank together stays below this (< 64 MB)
+DUMP_STREAMS = 16        # whole streams in its sample, at the most
+
+
+def stream_checksums(torch, buf, lens, width, rows=256):
+    """per stream k: sum over i < lens[k] of buf[k * width + i] * (i % 251 + 1), as float64
+    (exact: below 2^53); bytes past a stream's length (never written) do not count"""
+    S = lens.numel()
+    out = torch.zeros(S, dtype=torch.float64, device=buf.device)
+    col = torch.arange(width, device=buf.device)
+    weight = col % 251 + 1
+    v = buf.view(S, width)
+    for at in range(0, S, rows):
+        keep = col < lens[at:at + rows, None]
+        out[at:at + rows] = (v[at:at + rows].to(torch.int64) * weight * keep).sum(1).to(torch.float64)
+    return out
+
+
+def dump_outputs(torch, b, path, rank, world, total):
+    """--dump-outputs: what the last timed step left in the buffers its caller handed in, as
+    float .npy files under `path` (at N > 1 rank r appends _rank<r> to every name). With the same
+    arguments the inputs, and so these files, are the same from run to run.
+
+    For every stream of the shard (float32 status, float64 the rest): encode_status,
+    encoded_len, decode_status, decoded_len, and encoded_checksum / decoded_checksum
+    (stream_checksums over the stream's encoded / decoded bytes). For a fixed sample of whole
+    streams, the first of a permutation of the batch's stream indices drawn from a generator
+    seeded with 0x5EED: sample_streams (their indices in the batch, ascending), encoded_sample
+    and decoded_sample (their bytes back to back in that order, float32). The sample is as many
+    streams (at most DUMP_STREAMS) as fit in DUMP_BYTES beside the per-stream arrays with every
+    sampled stream at its encode capacity: 16 at C5, 51 MB at the very most."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    S, N, cap = b.S, b.N, b.cap
+    sfx = f"_rank{rank}" if world > 1 else ""
+
+    def save(name, t):
+        np.save(os.path.join(path, name + sfx + ".npy"), t.cpu().numpy())
+
+    for name in ("est", "bst"):
+        if hasattr(b, name):
+            save({"est": "encode_status", "bst": "decode_status"}[name], getattr(b, name).to(torch.float32))
+    save("encoded_len", b.elens.to(torch.float64))
+    save("decoded_len", b.blens.to(torch.float64))
+    save("encoded_checksum", stream_checksums(torch, b.enc, b.elens, cap))
+    save("decoded_checksum", stream_checksums(torch, b.back, b.blens, N))
+    room = DUMP_BYTES - 40 * total - 1024 * 10 * world
+    K = max(0, min(DUMP_STREAMS, total, room // (4 * (cap + N) + 8)))
+    g = torch.Generator().manual_seed(0x5EED)
+    picked = sorted(int(k) for k in torch.randperm(total, generator=g)[:K])
+    mine = [k - rank * S for k in picked if rank * S <= k < (rank + 1) * S]
+    elens, blens = b.elens.cpu(), b.blens.cpu()
+    u8 = torch.empty(0, dtype=torch.uint8, device=b.enc.device)
+    save("sample_streams", torch.tensor([k + rank * S for k in mine], dtype=torch.float64))
+    save("encoded_sample", torch.cat([u8] + [b.enc[k * cap:k * cap + int(elens[k])] for k in mine]).to(torch.float32))
+    save("decoded_sample", torch.cat([u8] + [b.back[k * N:k * N + int(blens[k])] for k in mine]).to(torch.float32))
+
+
 def weak_line(torch, hc, hcdist, args, dev, stream, rank, world, barrier, dry, use_diff, N):
     """N > 1: every rank codes a whole batch of its own (C5's 65536 streams; the dry run: --streams),
     streams k = r*S .. r*S + S - 1, timed like the headline (max over ranks), verified the same way.
@@ -906,6 +978,8 @@ def main(argv=None):
     b = StandInBatch(torch, rank * S, S, N) if dry else Batch(torch, hc, dev, args.kind, rank * S, S, use_diff)
     barrier = dist.barrier if dist.is_initialized() else None
     wall, enc_ms, dec_ms = timed(torch, b, stream, args.steps, args.warmup, barrier)
+    if args.dump_outputs:  # before the checks: a run that fails them still leaves its outputs to look at
+        dump_outputs(torch, b, args.dump_outputs, rank, world, total)
 
     # verification (outside the timed region): every status 0, exact sizes, exact bytes
     bad = b.bad()
@@ -943,11 +1017,11 @@ def main(argv=None):
         result["config"]["workload"] = f"dry run: {total} x {N}-byte streams over {world} rank(s) ({S} per rank)"
     if dist.is_initialized():
         result["process_group"] = {"backend": dist.get_backend(), "world": dist.get_world_size()}
-    if world == 1 and not dry:
+    if args.full and world == 1 and not dry:
         roof["measured_copy_GBps"] = copy_peak(torch, dev, stream)
     if args.gather:
         result["gather"] = time_gather(torch, hcdist, b, dev, barrier)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not dry:
         host = host_cpus()
         cores = host["usable"]
         sample = min(args.cpu_sample or 8 * cores, S)
@@ -967,11 +1041,11 @@ def main(argv=None):
     del b
     if not dry:
         torch.cuda.empty_cache()
-    if world > 1 and not args.no_weak_line:
+    if args.full and world > 1 and not args.no_weak_line:
         result["weak_scaling"] = weak_line(torch, hc, hcdist, args, dev, stream, rank, world, barrier, dry,
                                            use_diff, N)
     cbad = 0
-    if not dry and world == 1 and not args.no_configs:
+    if args.full and not dry and world == 1 and not args.no_configs:
         c5_kernel = S * N / ((enc_ms + dec_ms) * 1e-3) / 2**30 if S == C5_STREAMS and use_diff and \
             args.kind == "photo" else None
         configs, cbad = run_configs(torch, hc, dev, stream, set(), c5_kernel)

@@ -35,7 +35,7 @@ DATA = "/root/reference/data"
 MODES = {"c": ["-c"], "cm": ["-c", "-m"], "ca": ["-c", "-a"], "cma": ["-c", "-m", "-a"]}
 CORPUS_HUF = [("hd01", "c"), ("hd01", "cm"), ("hd01", "ca"), ("hd01", "cma"), ("df1h", "cm"),
               ("df1h", "cma"), ("df1v", "c"), ("df1v", "ca"), ("hd01extra", "cma"),
-              ("hd01double", "cm")]
+              ("hd01double", "cm"), ("df1hvx", "cm"), ("hd12", "cm")]
 
 
 def sha(b):

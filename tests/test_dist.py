@@ -142,12 +142,57 @@ def test_bench_multi_rank_dry_run(world, weak):
     S = 2 * world
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-           "--backend", "gloo", "--gpus", str(world), "--steps", "3", "--warmup", "1",
+           "--backend", "gloo", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--full",
            "--gather", "--dry-stream-bytes", str(N)] + (["--weak", "--streams", "2"] if weak else ["--total-streams", str(S)])
     env = dict(os.environ, OMP_NUM_THREADS="1")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     _check_dry_line(p.stdout, world, S, 2, weak, N, 2 if weak else S)
+
+
+def test_bench_plain_run_and_dump_outputs_dry_run(tmp_path):
+    """a plain run measures the headline only (nothing of --full in its line); --dump-outputs writes
+    the last step's outputs as float .npy files, the same from run to run, within 64 MB, and the
+    sampled streams are the stand-in's copies of the seeded inputs"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    sys.path.insert(0, root)
+    import bench
+    N, S = 1500, 40
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE",
+                                                              "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "1"
+    dumps = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--backend", "gloo", "--gpus", "1", "--steps", "4",
+               "--warmup", "1", "--dry-stream-bytes", str(N), "--streams", str(S), "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=120, env=env, cwd=root)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 4 and r["ms_per_step"] > 0 and r["unit"] == "GiB/s" and r["higher_is_better"] is True
+        assert r["dtype"] == "u8" and r["metric"].startswith(bench.METRIC) and r["value"] > 0
+        assert not {"cpu_baseline", "configs", "weak_scaling", "gather"} & set(r)
+        dumps.append({f.name: np.load(f) for f in sorted((tmp_path / d).iterdir())})
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 64_000_000
+    a, b = dumps
+    assert set(a) == set(b) == {n + ".npy" for n in ("encoded_len", "decoded_len", "encoded_checksum", "decoded_checksum",
+                                                      "sample_streams", "encoded_sample", "decoded_sample")}
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], b[name]), name
+    picked = a["sample_streams.npy"].astype(int).tolist()
+    assert len(picked) == bench.DUMP_STREAMS and picked == sorted(set(picked)) and 0 <= picked[0] and picked[-1] < S
+    want = torch.cat([bench.stand_in_stream(torch, k, N) for k in picked]).numpy()
+    assert np.array_equal(a["decoded_sample.npy"], want) and np.array_equal(a["encoded_sample.npy"], want)
+    assert a["encoded_len.npy"].tolist() == [N] * S == a["decoded_len.npy"].tolist()
+    w = np.arange(N) % 251 + 1
+    sums = [float((bench.stand_in_stream(torch, k, N).numpy().astype(np.int64) * w).sum()) for k in range(S)]
+    assert a["decoded_checksum.npy"].tolist() == sums == a["encoded_checksum.npy"].tolist()
 
 
 def test_bench_gpus_flag_launches_its_own_ranks():
@@ -163,7 +208,7 @@ def test_bench_gpus_flag_launches_its_own_ranks():
                                                               "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--backend", "gloo", "--gpus", "2", "--steps", "3",
-           "--warmup", "1", "--gather", "--dry-stream-bytes", str(N), "--total-streams", str(S)]
+           "--warmup", "1", "--full", "--gather", "--dry-stream-bytes", str(N), "--total-streams", str(S)]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     r = _check_dry_line(p.stdout, 2, S, S // 2, False, N, S)

@@ -1,17 +1,15 @@
 """The oracle (oracle/hc_oracle.c, a C restatement) pinned against the reference.
 
 Pinning: every golden vector and digest in tests/golden/ was produced by the reference binary
-itself (oracle/_ref/huffman-codec, built from /root/reference/src; see make_golden.py). When
-/root/reference is present (build container) the oracle is also checked against the reference
-corpus data/*.raw and against the freshly built reference binary.
+itself (see make_golden.py). The oracle is also checked on the reference's sample corpus, whose
+raw files are recovered from the reference's stored outputs for them, and, where the reference
+binary has been built (oracle/_ref), against that binary.
 """
 import hashlib
 import os
 
 import numpy as np
 import pytest
-
-from conftest import REF_DATA
 
 MODES = {"c": (False, False), "cm": (True, False), "ca": (False, True), "cma": (True, True)}
 
@@ -78,10 +76,14 @@ def test_oracle_corpus_huf_roundtrip(oracle_mod, digests):
         assert st == 0 and again == huf, fn
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference corpus not present (GPU box)")
 def test_oracle_corpus_digests(oracle_mod, digests):
-    for name in ("hd01", "df1hvx", "hd01extra", "hd12"):
-        raw = open(os.path.join(REF_DATA, name + ".raw"), "rb").read()
+    """the raw corpus files are not kept: each is recovered from the reference's own output for it
+    (tests/golden/corpus/*.huf) and must then have the raw file's digest"""
+    gdir = os.path.join(os.path.dirname(__file__), "golden", "corpus")
+    for name, fn in (("hd01", "hd01.cm.huf"), ("df1hvx", "df1hvx.cm.huf"), ("hd01extra", "hd01extra.cma.huf"),
+                     ("hd12", "hd12.cm.huf")):
+        st, raw = oracle_mod.decompress(open(os.path.join(gdir, fn), "rb").read())
+        assert st == 0 and len(raw) == digests["corpus"][name]["raw_len"]
         assert sha(raw) == digests["corpus"][name]["raw_sha256"]
         for m, (d, a) in MODES.items():
             st, out = oracle_mod.compress(raw, d, a, 512)
