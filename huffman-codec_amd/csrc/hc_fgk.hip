@@ -55,12 +55,17 @@ static uint32_t g_enc_tab = 0;
 // decoder launch for narrow streams: 0 = by payload rate (dec_small_stream), 1 = small-alphabet
 // for all, 2 = regular for all (hc_debug_set_dec_small)
 static uint32_t g_dec_small = 0;
+// the most codes one decoder batch step takes (Dec::decode_batch; hc_debug_set_dec_pack: 1, 7 or
+// HC_DEC_PACK)
+__device__ uint32_t g_dec_pack = 16;
+__device__ __forceinline__ uint32_t dec_pack_max(uint32_t k) { return min(k, (uint32_t)__builtin_amdgcn_readfirstlane(g_dec_pack)); }
 __device__ __forceinline__ uint64_t *trace_buf() { return g_trace; }
 __device__ __forceinline__ uint32_t window_bytes() { return __builtin_amdgcn_readfirstlane(g_window); }
 static uint32_t min_tree() { return g_min_tree; }
 static uint32_t enc_tab() { return g_enc_tab; }
 static uint32_t dec_small() { return g_dec_small; }
 #else
+__device__ __forceinline__ uint32_t dec_pack_max(uint32_t k) { return k; }
 __device__ __forceinline__ uint64_t *trace_buf() { return nullptr; }
 __device__ __forceinline__ uint32_t window_bytes() { return 1u << 30; }
 static uint32_t min_tree() { return 0; }
@@ -189,36 +194,48 @@ constexpr uint32_t kRow = 16;       // u16 per cache entry
 #ifndef HC_ENC_BATCH
 #define HC_ENC_BATCH 1
 #endif
-// decoder (narrow and wide layouts): up to HC_DEC_BATCH (<= 7) codes per step from one read of
-// the level tables at every bit offset and one tentative commit (Dec::decode_batch; 0: the
-// one-symbol loop only). Measured, C5 decode: one-symbol loop 490 ms, 6 per step 443, 7 per step
-// 430; eight per step in 8-lane groups (the root's increments apart) 437; a first code of >= 8
-// bits sent to the one-symbol step before the chain (HC_DEC_EXIT8): noise decode 237 -> 198 ms,
-// C5 +0.5 %
+// decoder (narrow and wide layouts): HC_DEC_BATCH != 0: up to HC_DEC_PACK (4, 8, 12 or 16) codes
+// per step, packed by bit offset (one lane per code bit), from one read of the level tables at
+// every bit offset and one tentative commit (Dec::decode_batch; HC_DEC_BATCH 0: the one-symbol
+// loop only). Measured on the earlier layout of nine lanes per code, C5 decode: one-symbol loop
+// 490 ms, 6 per step 443, 7 per step 430; eight per step in 8-lane groups (the root's increments
+// apart) 437; a first code of >= 8 bits sent to the one-symbol step before the chain
+// (HC_DEC_EXIT8): noise decode 237 -> 198 ms, C5 +0.5 %
 #ifndef HC_DEC_BATCH
 #define HC_DEC_BATCH 7
+#endif
+#ifndef HC_DEC_PACK
+#define HC_DEC_PACK 16
 #endif
 #ifndef HC_DEC_EXIT8
 #define HC_DEC_EXIT8 1
 #endif
-// 1: a batch whose first failing symbol's failure may be false (its test counts no earlier batch
-// symbol through the next position) is tested again from that symbol with the earlier ones
-// committed (code_all_batch, Dec::decode_batch; model: fgk_batch_model.retry_len)
-// (measured, grad / C5 / noise, ms: 1 with the plausibility test below, encode 1.50 -> 1.51 / +1 %
-// / +0.3 %, decode 1.64 -> 1.66 / +0.7 % / +1 %; 2, the miss test only: encode ±0 / +1.2 % / ±0,
-// decode -5.5 % / ±0 / +2 %: the retest's ~35-55 instructions cost what the restarts they save do;
-// the decoder's alone, in the blocks of streams that have seen <= 16 symbols (a second copy of the
-// block loop): grad decode -2.7 %, C5 decode +0.3 %, C3 decode +0.8 %)
+// (measured and dropped with the nine-lane layout, HC_BATCH_RETRY: a batch whose first failing
+// symbol's failure may be false -- its test counts no earlier batch symbol through the next
+// position -- tested again from that symbol with the earlier ones committed; model:
+// fgk_batch_model.retry_len. grad / C5 / noise: decode -5.5 % / +-0 / +2 % at best: the retest's
+// ~35-55 instructions cost what the restarts they save do)
 // the encoder vote's spread sample: eight segments' loads in flight at once (enc_mode_kernel)
 #ifndef HC_VOTE_BATCH
 #define HC_VOTE_BATCH 1
 #endif
-#ifndef HC_BATCH_RETRY
-#define HC_BATCH_RETRY 0
-#endif
 #ifndef HC_BATCH_YIELD
 #define HC_BATCH_YIELD 5
 #endif
+// Dec::run: a stream whose batches are off tries them again every HC_BATCH_PROBE-th block (a power
+// of two); HC_DEC_EXIT8: a first code of HC_DEC_EXIT_BITS bits or more leaves the step to the
+// one-symbol loop. A packed step costs two LDS round trips more than the nine-lane one did, which
+// the flat alphabets' few waves per SIMD wait out: with 8 blocks and 8 bits (the nine-lane
+// layout's values) noise decode was 167.0 ms and C3 156.5 against 161.8 and 154.6 before the
+// packed step (159.6 / 152.0 with no batches at all); 32 blocks alone 164.2 / 153.7, 7 bits alone
+// 164.4 / 156.6, both 161.5 / 154.4; C5 decode 367.4 against 365.7 ms
+#ifndef HC_BATCH_PROBE
+#define HC_BATCH_PROBE 32
+#endif
+#ifndef HC_DEC_EXIT_BITS
+#define HC_DEC_EXIT_BITS 7
+#endif
+static_assert((HC_BATCH_PROBE & (HC_BATCH_PROBE - 1)) == 0 && HC_DEC_EXIT_BITS >= 2 && HC_DEC_EXIT_BITS <= 8, "gate knobs");
 constexpr uint32_t kBatchYield = HC_BATCH_YIELD;  // Dec::run: twice the symbols per batch worth it
 // walk(): after a swap at a position lighter than this, the parent's level is walked at once
 // instead of chasing back to the known path. Measured (C5 encode / decode, noise encode /
@@ -2544,126 +2561,116 @@ struct Dec {
     }
 
 #if HC_DEC_BATCH
-    // Batched hot path (narrow and wide layouts; model: tests/fgk_batch_model.py decode_batch).
+    // Batched hot path (narrow and wide layouts; model: tests/fgk_pack_model.py decode_packed).
     // Between swaps and splits the tree's shape -- and with it every code -- is fixed, and the
     // update of a symbol whose levels all pass the leader test only adds 1 along its root path.
-    // So up to kB symbols are decoded in a row from the level tables alone (lane 9 j + l: level
-    // 8 - l of symbol j's lookup; one read per symbol, the window shifted by the depths read)
-    // and tested at once:
-    //  1. every batch symbol's path positions (each once: the lanes whose entry stops at their
-    //     own level; the root once per symbol) get their increment tentatively, one LDS add,
-    //     the words of the next positions having been read before;
+    // So up to kPackMax codes are decoded in a row from the level tables alone, packed by bit
+    // offset: lane o stands for bit o of the window, and the d lanes S..S + d - 1 of a d-bit code
+    // that starts at bit S read its path from depth 1 down to the leaf (lane o: the level-k entry
+    // of the k = o - S + 1 bits S..o, addressed as the one-symbol loop addresses it). No lane
+    // pads a short code, so a step takes as many codes as the window holds bits for; lane 63
+    // is the root. The step:
+    //  0. the depth of a code starting at every bit offset (the level-8 entries), the chain of
+    //     code starts S_j+1 = S_j + depth(S_j) on registers, and each lane's code index and
+    //     code start from the mask of start bits;
+    //  1. every code's path positions get their increment tentatively, one LDS add (the root
+    //     one per code, by lane 63), the words of the next positions having been read before;
     //  2. a level fails when that next word is below the position's word after the adds: the
     //     one-symbol loop's test with every batch symbol through the position counted as
     //     earlier (c0 at its largest) and none through the next one (c1 = 0), so it can report
-    //     a level falsely, never pass one that fails (the model: 2 % more symbols decoded alone
-    //     on a photo than with exact counts);
-    //  3. the increments of the first failing symbol and the ones after it are taken back. The
-    //     symbols before it are decoded; it -- or the first symbol whose entry is not a leaf (a
+    //     a level falsely, never pass one that fails;
+    //  3. the increments of the first failing code and the ones after it are taken back. The
+    //     codes before it are decoded; it -- or the first code whose entry is not a leaf (a
     //     code longer than the tables, or the NYT) -- goes to the one-symbol step.
-    // Returns whether the batch took every symbol the window and the block allowed (otherwise the
+    // Returns whether the batch took every code the window and the block allowed (otherwise the
     // one-symbol step takes the next one).
     __device__ __forceinline__ bool decode_batch(Idx i0, Idx &i, Idx i1)
     {
-        constexpr uint32_t kG = 9, kB = HC_DEC_BATCH;  // lanes per symbol (levels 8..0), symbols
-        static_assert(kB * kG <= 63, "batch lanes");
-        const uint32_t bj = lane < kB * kG ? lane / kG : 7u;  // the lane's symbol (7: idle)
-        const uint32_t bl = lane < kB * kG ? lane % kG : 8u;  // its level: 8 - bl
-        const uint32_t bsh = 24 + min(bl, 7u);
-        const uint32_t bvb = lds_off16(&fgk.T.lvl[0]) + 2 * (bl < 8 ? (256u >> bl) - 2 : 0xFFFFFFFEu);
-        const uint32_t l8 = lds_off16(&fgk.T.lvl[254]);  // level 8
+        constexpr uint32_t kPackMax = HC_DEC_PACK;  // codes per step
+        static_assert(kPackMax % 4 == 0 && kPackMax >= 4 && kPackMax <= 16, "chain chunks of four codes");
+        constexpr uint64_t kL63 = 1ull << 63;
         const uint64_t w0 = in.win;
-        const uint32_t n0 = in.nwin;  // >= 33: symbols 0..3 always fit
-        // lane o: the depth of a code that starts o bits into the window (its level-8 entry);
-        // the chain of symbol starts then runs on registers: S_j+1 = S_j + depth(S_j). sv lane j:
-        // the bits before symbol j.
+        const uint32_t n0 = in.nwin;  // >= 33
+        const uint32_t l8 = lds_off16(&fgk.T.lvl[254]);  // level 8
+        // lane o: the depth of a code that starts o bits into the window (its level-8 entry)
         const uint32_t dep = opaque(*(const lds_u16 *)(size_t)(l8 + 2 * (uint32_t)((w0 << lane) >> 56))) >> 10;
-#if HC_DEC_EXIT8
-        // a first code of 8 bits or more (most of them on a flat alphabet, e.g. noise, where codes
-        // are longer than the tables) goes to the one-symbol step at once
-        if (lane_read(dep, 0) >= 8) {
+        uint32_t S = lane_read(dep, 0);
+        // a first code of HC_DEC_EXIT_BITS bits or more (most of them on a flat alphabet, e.g. noise,
+        // where codes reach past the tables) goes to the one-symbol step at once; so does depth 0 (the
+        // tables of a tree that was the NYT alone: every entry the root, no code has a lane)
+        if (HC_DEC_EXIT8 ? S - 1 >= HC_DEC_EXIT_BITS - 1 : S == 0) {
             ++btry;
             return false;
         }
-#endif
-        // (measured and dropped: the chain by pointer doubling -- lane o's next start o + depth(o),
-        // composed by permutes, lane j applying them by the bits of j: 11 VALU + 4 LDS instead of
-        // ~16 VALU + 7 SALU, but its dependent permutes made C5 decode +0.8 %)
-        uint32_t S = 0, sv = 0;
-        const uint32_t bj4 = bj * 4;
+        // the chain of code starts: sv lane j = S_j, the bits before code j (255: no such code).
+        // Four codes per exit test; a code is taken only if it ends within the window's valid
+        // bits and within bit 62, so the chain ends once S passes lim. Past bit 63 the depths
+        // read are another offset's (the lane select wraps): S still grows, so those starts
+        // stay above lim.
+        // (measured and dropped on the 7 x 9 layout: the chain by pointer doubling, C5 decode
+        // +0.8 %)
+        const uint32_t lim = min(n0, 63u);
+        uint32_t sv = lane == 0 ? 0u : 255u;
+        sv = writelane(sv, S, 1);
 #pragma unroll
-        for (uint32_t j = 0; j < kB; ++j) {
-            sv = writelane(sv, S, j);
+        for (uint32_t j = 1; j < kPackMax; ++j) {
+            if (j % 4 == 0 && S >= lim) break;
             S += lane_read(dep, S);
+            sv = writelane(sv, S, j + 1);
         }
-        sv = writelane(sv, S, kB);
-        // each lane's own symbol's start: one permute (measured: C5 decode -5.5 % against a select
-        // per symbol in the chain, 14 VALU instructions per step)
-        const uint32_t sg = (uint32_t)__builtin_amdgcn_ds_bpermute((int)bj4, (int)sv);
-        // symbols whose code lies inside the window (lane j + 1: the bits up to symbol j's end)
-        const uint32_t nval = __builtin_popcountll(ballot(sv <= n0) & (((1ull << kB) - 1) << 1));
-        const uint32_t jmax = min(nval, (uint32_t)(i1 - i));
-        // every symbol's whole root path at once, each group on its own window
-        const uint32_t ent = opaque(*(const lds_u16 *)(size_t)(bvb + (((uint32_t)((w0 << sg) >> 32) >> bsh) << 1)));
-        const uint32_t pos = ent & 1023u;
-        // the lanes that add: each path position once (the entry stops at the lane's own level),
-        // symbols inside the window and the block
-        const uint64_t actm = ballot((ent >> 10) == 8 - bl) & groups9(jmax);
+        // codes inside the window (S_j+1 <= lim; the starts grow, so these are the first nval)
+        // and the block
+        const uint32_t nval = (uint32_t)__builtin_popcountll(ballot(sv <= lim)) - 1;
+        const uint32_t jmax = min(nval, dec_pack_max(min(kPackMax, (uint32_t)(i1 - i))));
+        const uint32_t se = lane_read(sv, jmax);  // the bits of the codes taken, <= 63
+        // the start bits as a mask: lane j sends a mark to lane S_j (the lanes without a code and
+        // the starts past bit 62 to lane 63, whose bit then only says that some code ends there
+        // or later); a code's leaf lane is the one before the next start
+        const uint64_t sm = ballot(__builtin_amdgcn_ds_permute((int)(min(sv, 63u) * 4), 1) != 0);
+        const uint64_t leaf = sm >> 1;
+        const uint64_t act = below_mask(se);  // the lanes of the codes taken
+        // the lane's code: the starts in bits 1..o; its start; its level
+        const uint32_t jv = __builtin_amdgcn_mbcnt_hi((uint32_t)(leaf >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)leaf, 0u));
+        uint32_t so = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(jv * 4), (int)sv);
+        so = sel(act, so, lane);  // idle lanes: level 1 of their own bit (a valid entry, not added)
+        const uint32_t k = lane + 1 - so;
+        // the level-k entry of bits so..o: index ((1 << k) | prefix) - 2
+        const uint32_t pre = __builtin_amdgcn_ubfe((uint32_t)(w0 >> (63 - lane)), 0, k);
+        const uint32_t ent = opaque(*(const lds_u16 *)(size_t)(lds_off16(&fgk.T.lvl[0]) - 4 + 2 * ((1u << k) + pre)));
+        const uint32_t pos = sel(kL63, kRoot, ent & 1023u);
+        // the lanes that add: every path position of the codes taken, and the root. An entry of
+        // level k <= the code's depth stops at level k in tables built whole, which is what a
+        // step reads; a lane where it does not (every lane of a code is a path position here, none
+        // pads) ends the batch at its code like a failing level, below.
+        const uint64_t actm = ballot((ent >> 10) == k) & act;
         constexpr uint32_t kI = kW ? 1u : 1024u;
         const uint32_t wa = lds_off(&fgk.T.wt[0]) + 4 * pos;
         const uint32_t scr = lds_off(fgk.scr32());
-        // a leaf's body is its symbol; bit 15: inner or NYT (read with the weights: a symbol whose
+        // a leaf's body is its symbol; bit 15: inner or NYT (read with the weights: a code whose
         // entry is no leaf has its increments taken back like a failing one)
         const uint32_t b = opaque(*(const lds_u16 *)(size_t)(lds_off16(&fgk.T.body[0]) + 2 * pos));
         const uint32_t w1 = *(const lds_u32 *)(size_t)(wa + 4);
-        __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(actm, wa, scr), kI, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_WAVEFRONT);
+        __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(actm | kL63, wa, scr), sel(kL63, jmax * kI, kI),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         const uint32_t wn = *(const lds_u32 *)(size_t)wa;
-        constexpr uint64_t kLeafLanes = 0x0040201008040201ull & ((1ull << (kB * kG)) - 1);
-        // (ff1 of no lane: 0xFFFFFFFF, above every batch)
-        const uint32_t jn = ff1(ballot(b & kNotLeaf) & kLeafLanes) / kG;
-        uint64_t ft = ballot(w1 < wn) & actm;
-        uint32_t jf = min(min(ff1(ft) / kG, jn), jmax);
-        if (jf < jmax) {
-            __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(actm & ~groups9(jf), wa, scr), 0u - kI,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#if HC_BATCH_RETRY
-            // 4. retest in place when the failure of symbol jf (a leaf) may be false, as the
-            // encoder's code_all_batch does: the symbols before it committed, the words of its a
-            // and a + 1 hold the earlier symbols' exact counts
-            uint32_t j0 = 0;
-            while (jf > j0 && jf < jn) {
-                const uint64_t gl = groups9(jf);
-#if HC_BATCH_RETRY == 1
-                const uint32_t fa = lane_read(pos, ff1(ft));
-                if (!((ballot(pos == fa + 1) & gl) | (ballot(pos == fa) & actm & ~groups9(jf + 1)))) {
-                    HC_CNT(4);
-                    break;
-                }
-#endif
-                HC_CNT(3);
-                const uint64_t am2 = actm & ~gl;  // symbols jf..
-                const uint32_t w1r = *(const lds_u32 *)(size_t)(wa + 4);
-                __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am2, wa, scr), kI, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_WAVEFRONT);
-                const uint32_t wnr = *(const lds_u32 *)(size_t)wa;
-                ft = ballot(w1r < wnr) & am2;
-                j0 = jf;
-                jf = min(min(ff1(ft) / kG, jn), jmax);
-                if (jf > j0) HC_CNT(6);
-                if (jf == jmax) break;
-                __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(actm & ~groups9(jf), wa, scr), 0u - kI,
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            }
-#endif
+        // the first lane of a failing level or of a leaf lane that holds no leaf: its code ends
+        // the batch (the root's next word is a sentinel: lane 63 never fails)
+        const uint64_t nl = ballot(b & kNotLeaf) & leaf & act;
+        const uint64_t fm = (ballot(w1 < wn) & actm) | nl | (act & ~actm);
+        uint32_t jf = jmax, sj = se;
+        if (fm) {
+            const uint32_t fl = ff1(fm);
+            jf = lane_read(jv, fl);
+            sj = lane_read(so, fl);
+            __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel((actm & (~0ull << sj)) | kL63, wa, scr),
+                                   sel(kL63, (jf - jmax) * kI, 0u - kI), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         }
         const uint32_t sb0 = (uint32_t)(size_t)(lds_u8 *)sbuf + (uint32_t)(i - i0);
-        *(lds_u8 *)(size_t)sel(kLeafLanes & groups9(jf), sb0 + bj, scr) = (uint8_t)b;
+        *(lds_u8 *)(size_t)sel(leaf & below_mask(sj), sb0 + jv, scr) = (uint8_t)b;
         __builtin_amdgcn_wave_barrier();
         HC_CNT(1);
         if (jf < jmax) HC_CNT(2);
-        if (jf == jn && jf < jmax) HC_CNT(5);
-        const uint32_t sj = lane_read(sv, jf);
+        if (nl && ff1(nl) == ff1(fm)) HC_CNT(5);
         in.win = w0 << sj;
         in.nwin = n0 - sj;
         i += jf;
@@ -2875,12 +2882,12 @@ struct Dec {
             // photos: codes at or past the tables' 8 bits) they stop short and the one-symbol
             // loop is faster (measured: C4 decode 2.02 s without batches, 3.52 s with them; a
             // lone wave waits out each batch's table reads). A block runs batches when the last
-            // block that ran them took at least kBatchYield / 2 symbols per batch, and every 8th
-            // block tries them again.
+            // block that ran them took at least kBatchYield / 2 symbols per batch, and every
+            // HC_BATCH_PROBE-th block tries them again.
             if constexpr (kW <= 1) {
                 if (btry) batch_on = 2 * bsym >= kBatchYield * btry;
                 bsym = btry = 0;
-                if (batch_on || ((uint32_t)(i0 >> 8) & 7u) == 0) {
+                if (batch_on || ((uint32_t)(i0 >> 8) & (HC_BATCH_PROBE - 1u)) == 0) {
                     decode<true>(i0, i, i1);
                     close_block(i0, i1);
                     continue;
@@ -3041,6 +3048,15 @@ extern "C" int hc_debug_set_dec_small(uint32_t mode)
     // 0: by payload rate, 1: the small-alphabet decoder for every narrow stream, 2: for none
     hc::g_dec_small = mode > 2 ? 0 : mode;
     return 0;
+}
+
+extern "C" int hc_debug_set_dec_pack(uint32_t max)
+{
+    // the most codes a decoder batch step takes in every later FGK launch on the current device
+    // (a device variable, like the window: other devices keep theirs): 1, 7, or anything else
+    // for the build's HC_DEC_PACK
+    uint32_t k = max == 1 || max == 7 ? max : 16u;
+    return hipMemcpyToSymbol(HIP_SYMBOL(hc::g_dec_pack), &k, sizeof(k)) == hipSuccess ? 0 : HC_ERR_DEVICE;
 }
 
 extern "C" int hc_debug_set_enc_tab(uint32_t mode)

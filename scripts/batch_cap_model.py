@@ -8,6 +8,15 @@ counted here: ten symbols of six lanes (depth <= 5) whenever the step's next ten
 that depth, else the present layout.
 
     python scripts/batch_cap_model.py [--stream 0] [--symbols 60000]
+
+--policy pack / hyst: the two layouts the kernels can realise without an oracle
+(tests/fgk_pack_model.py) on streams 0..3 -- the decoder packed by bit offset (one lane per code
+bit, up to 16 or 12 codes per step, the 64-bit window refilled by 32 at <= 32 valid bits), the
+encoder's 9 x 7 / 7 x 9 layouts chosen by hysteresis -- against the 7 x 9 steps: steps, symbols per
+step, symbols coded alone.
+
+    python scripts/batch_cap_model.py --policy pack
+    python scripts/batch_cap_model.py --policy hyst
 """
 import argparse
 import os
@@ -71,11 +80,43 @@ def run(symbols, encoder, layout):
     return st
 
 
+def realisable(policy, n_sym):
+    import fgk_pack_model as P
+
+    def line(name, n, steps, alone, base=None):
+        rel = f" ({(steps / base - 1) * 100:+.1f} %)" if base else ""
+        print(f"  {name}: {steps} steps{rel}, {n / steps:.2f} symbols a step, {alone} alone")
+
+    for k in range(4):
+        syms = np.frombuffer(oracle.rle(oracle.diff(oracle.synth("photo", k))), np.uint8)[:n_sym].tolist()
+        n = len(syms)
+        print(f"photo -c -m stream {k}, first {n} symbols")
+        if policy == "pack":
+            t0, s0 = P.decode_packed(syms, cap=7, window=False, exit8=False)
+            line("decoder 7 x 9", n, s0["steps"], s0["alone"])
+            for cap in (16, 12):
+                t1, s1 = P.decode_packed(syms, cap=cap, exit8=False)
+                assert t1.w == t0.w and t1.body == t0.body
+                line(f"decoder packed, <= {cap} codes", n, s1["steps"], s1["alone"], s0["steps"])
+            t1, s1 = P.decode_packed(syms, cap=16, window=False, exit8=False)
+            line("decoder packed, <= 16 codes, no window limit", n, s1["steps"], s1["alone"], s0["steps"])
+        else:
+            c0, t0, s0 = P.encode_hyst(syms, 1)
+            line("encoder 7 x 9", n, s0["steps"], s0["alone"])
+            c1, t1, s1 = P.encode_hyst(syms, 0)
+            assert c1 == c0 and t1.w == t0.w
+            line("encoder 9 x 7 / 7 x 9 by hysteresis", n, s1["steps"], s1["alone"], s0["steps"])
+            print(f"    {s1['shallow']} shallow steps, {s1['switches']} switches, {s1['empty']} steps that took nothing")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stream", type=int, default=0)
     ap.add_argument("--symbols", type=int, default=60000)
+    ap.add_argument("--policy", choices=("oracle", "pack", "hyst"), default="oracle")
     a = ap.parse_args()
+    if a.policy != "oracle":
+        return realisable(a.policy, a.symbols)
     syms = np.frombuffer(oracle.rle(oracle.diff(oracle.synth("photo", a.stream))), np.uint8)[: a.symbols].tolist()
     for name, enc in (("encoder (path cache)", True), ("decoder (level tables)", False)):
         # the deepest batch path: the encoder's cached rows (insert depth 9), the decoder's tables

@@ -9,7 +9,7 @@
 
     python scripts/profile_artifacts.py <tag> <round> [--streams S] [--mode cm] [--kind photo]
 
-HBM bytes = FETCH_SIZE x 2 + WRITE_SIZE (KB -> B). The x2: on gfx950 FETCH_SIZE counts half of
+Per-launch figures are medians over a kernel's launches. HBM bytes = FETCH_SIZE x 2 + WRITE_SIZE (KB -> B). The x2: on gfx950 FETCH_SIZE counts half of
 wide streaming reads (MI355X_MICROARCH.md, HBM / rocprofv3); the kernels' loads are 4 B/lane,
 which the guide lists as uncalibrated, so the factor is checked against a known byte count: the
 encoder reads exactly streams x 262144 raw bytes, and x2 FETCH_SIZE reproduces that (the check
@@ -24,6 +24,7 @@ import json
 import os
 import re
 import shutil
+import statistics
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FGK_SRC = os.path.join(ROOT, "huffman-codec_amd", "csrc", "hc_fgk.hip")
@@ -70,16 +71,18 @@ def main():
     if stats:
         shutil.copy(stats[0], os.path.join(out, f"{a.round}_kernel_stats.csv"))
 
-    agg = collections.defaultdict(lambda: collections.defaultdict(float))
-    launches = collections.defaultdict(set)
+    # per kernel and counter: the value of every launch (a counter's rows of one dispatch summed).
+    # The per-launch figure is the median over the launches, not the mean: counters come from
+    # passes of their own, and a launch whose role differs from the others' (the path-cache
+    # encoder coding every stream in one step of a -c run, idle in the rest) may fall into one
+    # pass and not into another, which a mean would mix into figures that belong to no launch
+    per_launch = collections.defaultdict(lambda: collections.defaultdict(lambda: collections.defaultdict(float)))
     for f in glob.glob(os.path.join(prof, f"{a.tag}_pmc_*", "*counter_collection.csv")):
         for r in csv.DictReader(open(f)):
             k = kernel_key(r["Kernel_Name"])
             if not k or not k[1]:  # the narrow variants code the photo streams; the wide ones exit
                 continue
-            name = k[0]
-            agg[name][r["Counter_Name"]] += float(r["Counter_Value"])
-            launches[(name, r["Counter_Name"])].add(r["Dispatch_Id"])
+            per_launch[k[0]][r["Counter_Name"]][r["Dispatch_Id"]] += float(r["Counter_Value"])
     syms = a.symbols * a.streams
     src = hashlib.sha256(open(FGK_SRC, "rb").read()).hexdigest()[:16]
     summary = {"workload": f"bench.py --streams {a.streams} ({a.kind} -{a.mode.replace('m', ' -m')}, 512x512); "
@@ -90,8 +93,8 @@ def main():
     bench = {"source_sha": src, "launches": {},
              "_note": f"per-launch HBM bytes (FETCH_SIZE x2 + WRITE_SIZE) and SQ_INSTS_VALU + SQ_INSTS_SALU from "
                       f"rocprofv3 PMC passes; details in profiles/{a.round}_pmc_summary.json"}
-    for name, d in agg.items():
-        per = {c: v / max(1, len(launches[(name, c)])) for c, v in d.items()}
+    for name, d in per_launch.items():
+        per = {c: statistics.median(v.values()) for c, v in d.items()}
         summary["counters"][name] = per
         summary["per_symbol"][name] = {c: round(per[c] / syms, 3) for c in per
                                        if c.startswith("SQ_INSTS") or c.startswith("SQ_ACTIVE") or
