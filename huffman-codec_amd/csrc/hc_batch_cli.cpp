@@ -3,7 +3,7 @@
 // process, main.cpp:202-220). Each output is byte-identical to what `huffman-codec` (and the
 // reference) writes for that file alone.
 //
-//   huffman-codec-batch [-c | -d] [-m] [-a [-w WIDTH]] [-o OUTDIR] [-j THREADS] FILE...
+//   huffman-codec-batch [-c | -d] [-m] [-a [-w WIDTH]] [-s BYTES] [-o OUTDIR] [-j THREADS] FILE...
 //
 // Compression writes FILE.huf, decompression FILE without its .huf suffix (else FILE.out);
 // with -o into OUTDIR under the same base name. Files are read and written by a pool of
@@ -11,6 +11,11 @@
 // call: hc_compress_host_batch, hc_compress_adapt_host_batch (-a: one matrix of width WIDTH per
 // file) or hc_decompress_host_batch (any mix of adaptive and plain streams). A file that fails reports
 // "FILE: <the reference's message>"; the exit code is the first failing status (0: all ok).
+//
+// -s BYTES with -c writes every FILE.huf as a segmented container (HCSEG1, hcodec.h) of BYTES-byte
+// segments (0: the default size), one hc_seg_compress call per file. -d tells containers from
+// plain streams by their first 8 bytes and sends them through hc_seg_decompress_alloc; a failing
+// segment reports "FILE: segment K: <message>".
 #include <unistd.h>
 
 #include <algorithm>
@@ -31,8 +36,8 @@ namespace {
 
 const char *const kHelp =
     "USAGE:\n"
-    "  huffman-codec-batch [-cm] [-o OUTDIR] [-j THREADS] FILE...\n"
-    "  huffman-codec-batch [-cm] -a [-w WIDTH] [-o OUTDIR] [-j THREADS] FILE...\n"
+    "  huffman-codec-batch [-cm] [-s BYTES] [-o OUTDIR] [-j THREADS] FILE...\n"
+    "  huffman-codec-batch [-cm] -a [-w WIDTH] [-s BYTES] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch -d [-o OUTDIR] [-j THREADS] FILE... | -h\n"
     "\n"
     "OPTION:\n"
@@ -40,6 +45,7 @@ const char *const kHelp =
     "  -m     use differential model for preprocessing\n"
     "  -a     use adaptive block RLE (default: RLE)\n"
     "  -w     width of 2D data (default: 512)\n"
+    "  -s     write segmented containers of BYTES-byte segments (0: 65536)\n"
     "  -o     output directory (default: next to each input)\n"
     "  -j     file I/O threads (default: 8)\n"
     "  -h     show this help\n"
@@ -77,18 +83,23 @@ void parallel(size_t n, unsigned threads, F &&f)
 
 int main(int argc, char *argv[])
 {
-    bool compress = true, use_diff = false, use_adapt = false;
+    bool compress = true, use_diff = false, use_adapt = false, segmented = false;
+    uint64_t seg_bytes = 0;
     std::string dir;
     uint64_t width = 512;
     unsigned threads = 8;
     int opt;
-    while ((opt = getopt(argc, argv, ":cdmaw:o:j:h")) != -1) {
+    while ((opt = getopt(argc, argv, ":cdmaw:s:o:j:h")) != -1) {
         switch (opt) {
         case 'c': compress = true; break;
         case 'd': compress = false; break;
         case 'm': use_diff = true; break;
         case 'a': use_adapt = true; break;
         case 'w': width = std::stoull(optarg); break;
+        case 's':
+            segmented = true;
+            seg_bytes = std::stoull(optarg);
+            break;
         case 'o': dir = optarg; break;
         case 'j': threads = (unsigned)std::stoul(optarg); break;
         case 'h': std::cout << kHelp; return 0;
@@ -108,6 +119,7 @@ int main(int argc, char *argv[])
     const size_t n = files.size();
     std::vector<std::vector<uint8_t>> in(n), out(n);
     std::vector<int> status(n, 0);
+    std::vector<uint64_t> bad_seg(n, UINT64_MAX);  // the failing segment of a container
     parallel(n, threads, [&](size_t i) {
         std::ifstream ifs(files[i], std::ios::in | std::ios::binary);
         if (ifs.fail()) {
@@ -117,7 +129,16 @@ int main(int argc, char *argv[])
         in[i].assign(std::istreambuf_iterator<char>(ifs), std::istreambuf_iterator<char>());
     });
 
-    if (compress) {  // -a: one matrix of width `width` per file
+    if (compress && segmented) {  // one container per file, file after file
+        for (size_t i = 0; i < n; ++i) {
+            if (status[i]) continue;
+            out[i].resize(hc_seg_compress_bound(in[i].size(), seg_bytes, use_adapt, width));
+            uint64_t len = 0;
+            status[i] = hc_seg_compress(in[i].data(), in[i].size(), use_diff, use_adapt, width, seg_bytes,
+                                        out[i].data(), out[i].size(), &len);
+            out[i].resize(status[i] ? 0 : len);
+        }
+    } else if (compress) {  // -a: one matrix of width `width` per file
         std::vector<const uint8_t *> ip(n);
         std::vector<uint8_t *> op(n);
         std::vector<uint64_t> il(n), oc(n), ol(n), wd(n, width);
@@ -145,9 +166,20 @@ int main(int argc, char *argv[])
     } else {
         // one batch (adaptive and plain streams alike), whose output sizes are unknown up
         // front: a guess, then the exact size for those that report it
+        static const uint8_t kSegMagic[8] = {0x48, 0x43, 0x53, 0x45, 0x47, 0x31, 0x00, 0xFF};
         std::vector<size_t> batch;
-        for (size_t i = 0; i < n; ++i)
-            if (!status[i]) batch.push_back(i);
+        for (size_t i = 0; i < n; ++i) {
+            if (status[i]) continue;
+            if (in[i].size() < 8 || !std::equal(kSegMagic, kSegMagic + 8, in[i].begin())) {
+                batch.push_back(i);
+                continue;
+            }
+            uint8_t *p = nullptr;  // a segmented container
+            uint64_t len = 0;
+            status[i] = hc_seg_decompress_alloc(in[i].data(), in[i].size(), &p, &len, &bad_seg[i]);
+            if (!status[i]) out[i].assign(p, p + len);
+            hc_free(p);
+        }
         for (int pass = 0; pass < 2 && !batch.empty(); ++pass) {
             const size_t m = batch.size();
             std::vector<const uint8_t *> ip(m);
@@ -191,7 +223,8 @@ int main(int argc, char *argv[])
             return;
         }
         if (status[i]) {
-            msgs[i] = files[i] + ": " + hc_status_message(status[i]);
+            msgs[i] = files[i] + ": " + (bad_seg[i] != UINT64_MAX ? "segment " + std::to_string(bad_seg[i]) + ": " : "") +
+                      hc_status_message(status[i]);
             return;
         }
         const std::string op = out_path(files[i], compress, dir);

@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <utility>
+#include <vector>
+
 #include "hcodec.h"
 
 namespace hc {
@@ -52,5 +56,87 @@ uint64_t adapt_decode_work_bound(uint64_t total_in, uint64_t total_out, uint32_t
 // frees the host-batch pipeline slots' cached buffers (hc_release_cached; slots in use by a
 // running call are left alone)
 void pipe_release();
+
+
+// Device scratch of the single-buffer API. A call takes buffers from a per-device free list
+// (hipMalloc only when none is large enough) and gives them back at its end, so a process that
+// codes file after file (the CLI, C2) stops allocating after its first call. The list keeps at
+// most kKeepBytes per device (larger leftovers are freed at once) and hc_release_cached() frees
+// it. It caches memory only: no result depends on it, and concurrent calls never share a buffer.
+constexpr uint64_t kKeepBytes = 1ull << 30;
+struct FreeList {
+    std::mutex mu;
+    std::vector<std::pair<void *, uint64_t>> bufs[64];  // per device: (pointer, bytes)
+    uint64_t kept[64] = {};
+};
+inline FreeList &free_list()
+{
+    static FreeList *const f = new FreeList;  // never destroyed: the HIP runtime may be gone at exit
+    return *f;
+}
+
+struct DevBuf {
+    void *p = nullptr;
+    uint64_t cap = 0;
+    int dev = -1;
+    ~DevBuf() { give_back(); }
+    void give_back()
+    {
+        if (!p) return;
+        // the single-buffer API runs on the null stream; a call that returns early (an error
+        // after an asynchronous launch) may still have kernels writing this buffer, so wait for
+        // them before the next call can take it
+        (void)hipStreamSynchronize(nullptr);
+        FreeList &f = free_list();
+        {
+            std::lock_guard<std::mutex> lk(f.mu);
+            if (dev >= 0 && dev < 64 && f.kept[dev] + cap <= kKeepBytes) {
+                f.bufs[dev].emplace_back(p, cap);
+                f.kept[dev] += cap;
+                p = nullptr;
+            }
+        }
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    // at least n bytes: the smallest cached buffer that fits, else a new one (one retry after
+    // freeing the cache when the device is short of memory)
+    hipError_t alloc(uint64_t n)
+    {
+        give_back();
+        n = n < 16 ? 16 : (n + 255) & ~255ull;
+        if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+        if (dev >= 0 && dev < 64) {
+            FreeList &f = free_list();
+            std::lock_guard<std::mutex> lk(f.mu);
+            auto &v = f.bufs[dev];
+            size_t best = v.size();
+            for (size_t k = 0; k < v.size(); ++k)
+                if (v[k].second >= n && (best == v.size() || v[k].second < v[best].second)) best = k;
+            if (best != v.size()) {
+                p = v[best].first;
+                cap = v[best].second;
+                f.kept[dev] -= cap;
+                v.erase(v.begin() + (long)best);
+                return hipSuccess;
+            }
+        }
+        hipError_t e = hipMalloc(&p, n);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            hc_release_cached();
+            e = hipMalloc(&p, n);
+        }
+        cap = e == hipSuccess ? n : 0;
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    template <class T>
+    T *as() const
+    {
+        return reinterpret_cast<T *>(p);
+    }
+};
 
 }  // namespace hc

@@ -34,11 +34,21 @@ HC_ERR_CAPACITY = 64
 HC_ERR_UNSUPPORTED = 65
 HC_ERR_BLOCK_SIZE = 66
 HC_ERR_TOO_LARGE = 67
+HC_ERR_SEG_HEADER = 68
+HC_ERR_SEG_SIZE = 69
 HC_ERR_DEVICE = 70
 HC_ERR_ARG = 71
 
 HC_FLAG_DIFF = 0x80
 HC_FLAG_ADAPT = 0x40
+HC_SEG_DEFAULT_BYTES = 65536
+NO_SEGMENT = 2**64 - 1   # bad_segment when no segment failed
+
+
+class SegInfo(ctypes.Structure):
+    """hc_seg_info_t: the header fields of a segmented container"""
+    _fields_ = [("raw_len", ctypes.c_uint64), ("seg_bytes", ctypes.c_uint64), ("width", ctypes.c_uint64),
+                ("n_segments", ctypes.c_uint64), ("flags", ctypes.c_uint32)]
 
 SYNTH = {"noise": 0, "grad": 1, "photo": 2}
 
@@ -114,6 +124,18 @@ def _load(path):
     L.hc_device_info.argtypes = [ctypes.c_char_p, u64]
     L.hc_device_info.restype = ctypes.c_int
     L.hc_synth_batch.argtypes = [ctypes.c_int, u64, ctypes.c_uint32, u64, u64, vp, u64, vp]
+    for f in (L.hc_seg_count, L.hc_seg_compress_bound, L.hc_seg_compress_work_bound):
+        f.argtypes = [u64, u64, ctypes.c_int, u64]
+        f.restype = u64
+    L.hc_seg_info.argtypes = [u8p, u64, ctypes.POINTER(SegInfo)]
+    L.hc_seg_compress.argtypes = [u8p, u64, ctypes.c_int, ctypes.c_int, u64, u64, u8p, u64, ctypes.POINTER(u64)]
+    L.hc_seg_decompress.argtypes = [u8p, u64, u8p, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.hc_seg_decompress_alloc.argtypes = [u8p, u64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u64),
+                                          ctypes.POINTER(u64)]
+    L.hc_seg_compress_dev.argtypes = [vp, u64, ctypes.c_uint32, u64, u64, vp, u64, vp, vp, vp, u64, vp]
+    L.hc_seg_decompress_work_bound.argtypes = [ctypes.POINTER(SegInfo), u64]
+    L.hc_seg_decompress_work_bound.restype = u64
+    L.hc_seg_decompress_dev.argtypes = [vp, u64, ctypes.POINTER(SegInfo), vp, u64, vp, vp, vp, vp, u64, vp]
     _libs[path] = L
     return L
 
@@ -282,6 +304,126 @@ def decompress_adapt_batch(inp, in_offs, in_lens, out, out_offs, out_caps, out_l
                                          _stream_handle(stream))
     if rc:
         raise HCodecError(f"hc_decompress_adapt_batch failed: {rc}")
+    return work
+
+
+def seg_count(n, seg_bytes=0, use_adapt=False, width=512):
+    """hc_seg_count: segments of an n-byte input (0: invalid arguments)"""
+    return int(lib().hc_seg_count(n, seg_bytes, int(bool(use_adapt)), width))
+
+
+def seg_compress_bound(n, seg_bytes=0, use_adapt=False, width=512):
+    return int(lib().hc_seg_compress_bound(n, seg_bytes, int(bool(use_adapt)), width))
+
+
+def seg_info(data):
+    """hc_seg_info (host only, no device): (status, SegInfo or None) of a container's header"""
+    b, p = _buf(data)
+    info = SegInfo()
+    st = lib().hc_seg_info(p, len(b), ctypes.byref(info))
+    return st, (info if st == 0 else None)
+
+
+def seg_compress(data, use_diff=False, use_adapt=False, width=512, seg_bytes=0, cap=None):
+    """hc_seg_compress: (status, HCSEG1 container) of one input coded as parallel segments.
+    cap: the output capacity (default: hc_seg_compress_bound)."""
+    b, p = _buf(data)
+    if cap is None:
+        cap = lib().hc_seg_compress_bound(len(b), seg_bytes if seg_bytes % 16 == 0 else 0,
+                                          int(bool(use_adapt)), width)
+    out = ctypes.create_string_buffer(max(int(cap), 1))
+    n = ctypes.c_uint64(0)
+    st = lib().hc_seg_compress(p, len(b), int(bool(use_diff)), int(bool(use_adapt)), width, seg_bytes,
+                               ctypes.cast(out, ctypes.c_void_p), cap, ctypes.byref(n))
+    return st, (out.raw[:n.value] if st == 0 else b"")
+
+
+def seg_decompress(data, full=False):
+    """hc_seg_decompress_alloc: (status, decoded bytes); full: (status, bytes, out_len, bad_segment)"""
+    b, p = _buf(data)
+    q = ctypes.c_void_p()
+    n = ctypes.c_uint64(0)
+    bad = ctypes.c_uint64(0)
+    st = lib().hc_seg_decompress_alloc(p, len(b), ctypes.byref(q), ctypes.byref(n), ctypes.byref(bad))
+    out = b""
+    if st == 0:
+        out = ctypes.string_at(q, n.value) if n.value else b""
+    if q:
+        lib().hc_free(q)
+    return (st, out, n.value, bad.value) if full else (st, out)
+
+
+def _check_seg(inp, out, out_len, status, bad_segment):
+    """the tensor checks of _check_batch for the segmented device calls (one result each)"""
+    import torch
+    spec = [("in", inp, torch.uint8, None), ("out", out, torch.uint8, None), ("out_len", out_len, torch.int64, 1),
+            ("status", status, torch.int32, 1)]
+    if bad_segment is not None:
+        spec.append(("bad_segment", bad_segment, torch.int64, 1))
+    dev = inp.device if isinstance(inp, torch.Tensor) else None
+    for name, t, dt, numel in spec:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch tensor")
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"{name}: expected a CUDA tensor on {dev}, got {t.device}")
+        if t.dtype != dt:
+            raise TypeError(f"{name}: expected {dt}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: not contiguous")
+        if numel is not None and t.numel() != numel:
+            raise ValueError(f"{name}: {t.numel()} entries, expected {numel}")
+    for name, t in (("in", inp), ("out", out)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name}: must be 16-byte aligned")
+
+
+def seg_compress_dev(inp, out, out_len, status, use_diff=False, use_adapt=False, width=512, seg_bytes=0,
+                     stream=None, work=None, out_cap=None):
+    """hc_seg_compress_dev on CUDA tensors: the whole of `inp` (uint8) into one container in `out`
+    (capacity out_cap, default all of it); out_len (int64[1]) and status (int32[1]) are device
+    results, asynchronous on `stream`. The workspace is allocated here unless given. Returns it."""
+    _check_seg(inp, out, out_len, status, None)
+    cap = out.numel() if out_cap is None else int(out_cap)
+    if cap > out.numel():
+        raise ValueError(f"out_cap {cap} exceeds the {out.numel()}-byte output tensor")
+    flags = (HC_FLAG_DIFF if use_diff else 0) | (HC_FLAG_ADAPT if use_adapt else 0)
+    need = int(lib().hc_seg_compress_work_bound(inp.numel(), seg_bytes, int(bool(use_adapt)), width))
+    if work is None:
+        work = _work(need, inp.device)
+    _check_work(work, inp.device, need)
+    rc = lib().hc_seg_compress_dev(_dp(inp), inp.numel(), flags, width, seg_bytes, _dp(out), cap, _dp(out_len),
+                                   _dp(status), _dp(work), work.numel(), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_seg_compress_dev failed: {rc}")
+    return work
+
+
+def seg_decompress_dev(inp, out, out_len, status, bad_segment=None, info=None, stream=None, work=None,
+                       in_len=None, out_cap=None):
+    """hc_seg_decompress_dev on CUDA tensors: the container in inp[:in_len] into `out` (capacity
+    out_cap, default all of it). info: the container's SegInfo; when not given, the 48 header
+    bytes are copied down (a synchronising copy) and parsed here; a header that does not parse
+    is passed on as it is and the device status reports HC_ERR_SEG_HEADER. Returns the workspace."""
+    _check_seg(inp, out, out_len, status, bad_segment)
+    n = inp.numel() if in_len is None else int(in_len)
+    if n > inp.numel():
+        raise ValueError(f"in_len {n} exceeds the {inp.numel()}-byte input tensor")
+    cap = out.numel() if out_cap is None else int(out_cap)
+    if cap > out.numel():
+        raise ValueError(f"out_cap {cap} exceeds the {out.numel()}-byte output tensor")
+    if info is None:
+        head, p = _buf(inp[:min(n, 48)].cpu().numpy().tobytes())
+        info = SegInfo()  # stays all zero when the header does not parse: the call rejects it
+        lib().hc_seg_info(p, n, ctypes.byref(info))
+    need = int(lib().hc_seg_decompress_work_bound(ctypes.byref(info), n))
+    if work is None:
+        work = _work(need, inp.device)
+    _check_work(work, inp.device, need)
+    rc = lib().hc_seg_decompress_dev(_dp(inp), n, ctypes.byref(info), _dp(out), cap, _dp(out_len), _dp(status),
+                                     ctypes.c_void_p(None) if bad_segment is None else _dp(bad_segment),
+                                     _dp(work), work.numel(), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_seg_decompress_dev failed: {rc}")
     return work
 
 

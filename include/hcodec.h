@@ -41,6 +41,8 @@ enum hc_status {
     HC_ERR_UNSUPPORTED = 65,  /* -a stream given to a non-adaptive entry point or vice versa */
     HC_ERR_BLOCK_SIZE = 66,   /* forged adaptive header, block size 0 (reference: SIGFPE)    */
     HC_ERR_TOO_LARGE = 67,    /* forged adaptive header, W*H > 2^36 (reference: bad_alloc)   */
+    HC_ERR_SEG_HEADER = 68,   /* segmented container: bad header, index or length            */
+    HC_ERR_SEG_SIZE = 69,     /* segmented container: a segment decodes to another length    */
     HC_ERR_DEVICE = 70,       /* HIP runtime error / no gfx950 device                        */
     HC_ERR_ARG = 71           /* null pointer, misaligned device buffer, bad flag            */
 };
@@ -177,6 +179,81 @@ int hc_decompress_host_batch(const uint8_t *const *in, const uint64_t *in_lens, 
  * overlap. No reference counterpart (the reference writes one file per process). */
 int hc_pack_batch(const uint8_t *in, const uint64_t *in_offs, const uint64_t *lens, uint32_t n_streams,
                   uint8_t *out, const uint64_t *out_offs, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Segmented container (HCSEG1) — one large input coded as many independent segments in one
+ * batch launch. A format of this library (the reference has none); opt-in: no other entry point
+ * reads or writes it, and a container handed to hc_decompress* gets HC_ERR_HUFFMAN like any
+ * stream whose count is above 2^63. All integers little-endian, offsets from the start:
+ *
+ *   0   8   magic  48 43 53 45 47 31 00 FF ("HCSEG1\0\xFF")
+ *   8   1   flags  HC_FLAG_DIFF | HC_FLAG_ADAPT, other bits 0
+ *   9   7   zero
+ *   16  8   raw_len     decoded bytes in total
+ *   24  8   seg_bytes   the segment size given to the encoder (multiple of 16, >= 16)
+ *   32  8   width       adaptive: matrix width; otherwise 0
+ *   40  8   n_segments  >= 1
+ *   48  8n  enc_len[k]  byte length of segment k's stream
+ *   then the segments in order, each at the next multiple of 16 (padding bytes 0); the
+ *   container ends with the last byte of the last segment.
+ *
+ * Segment k is exactly the stream hc_compress writes for segment k's bytes alone with the same
+ * options. The cuts are a function of raw_len, seg_bytes, flags and width: plain, segment k is
+ * raw bytes [k seg_bytes, min((k+1) seg_bytes, raw_len)), n = max(1, ceil(raw_len / seg_bytes));
+ * adaptive, the segments are bands of rows = max(8, floor(seg_bytes / width) & ~3) rows, each
+ * coded as its own width x rows matrix, and a band that would leave fewer than 8 rows takes
+ * those too.
+ * ------------------------------------------------------------------------------------- */
+#define HC_SEG_DEFAULT_BYTES 65536u
+typedef struct hc_seg_info_t {
+    uint64_t raw_len, seg_bytes, width, n_segments;
+    uint32_t flags;
+} hc_seg_info_t;
+
+/* Segments of an in_len-byte input (seg_bytes 0: HC_SEG_DEFAULT_BYTES); 0 when the arguments
+ * are invalid (seg_bytes not a multiple of 16; adaptive: width 0, in_len not a multiple of
+ * width, width or height < 8). */
+uint64_t hc_seg_count(uint64_t in_len, uint64_t seg_bytes, int use_adapt, uint64_t width);
+/* Worst-case container size (0 when invalid). */
+uint64_t hc_seg_compress_bound(uint64_t in_len, uint64_t seg_bytes, int use_adapt, uint64_t width);
+/* Host only, no device: parses and checks the 48 header bytes against in_len (every header rule,
+ * 48 + 8 n <= in_len, raw_len <= 520 in_len). HC_OK and *info, or HC_ERR_SEG_HEADER. */
+int hc_seg_info(const uint8_t *in, uint64_t in_len, hc_seg_info_t *info);
+
+/* Host buffers, synchronous. seg_bytes 0: HC_SEG_DEFAULT_BYTES. Returns HC_ERR_ARG (null
+ * pointer, seg_bytes not a multiple of 16), then HC_ERR_WIDTH, HC_ERR_MATRIX_SIZE, HC_ERR_DIMS
+ * as hc_compress, HC_ERR_DEVICE, HC_ERR_CAPACITY (*out_len = needed). */
+int hc_seg_compress(const uint8_t *in, uint64_t in_len, int use_diff, int use_adapt, uint64_t width,
+                    uint64_t seg_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+/* HC_ERR_SEG_HEADER (bad container; *out_len = 0), HC_ERR_CAPACITY (*out_len = raw_len), the
+ * status of the lowest failing segment with *bad_segment its index (a segment that wants
+ * another length than its cut: HC_ERR_SEG_SIZE), or HC_OK. *bad_segment (may be NULL) is
+ * UINT64_MAX unless a segment failed. */
+int hc_seg_decompress(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
+                      uint64_t *out_len, uint64_t *bad_segment);
+/* Same, with the output allocated by the library (release with hc_free). */
+int hc_seg_decompress_alloc(const uint8_t *in, uint64_t in_len, uint8_t **out, uint64_t *out_len,
+                            uint64_t *bad_segment);
+
+/* Device buffers, asynchronous on `stream`; in, out and work 16-byte aligned; out_len, status
+ * and bad_segment are DEVICE pointers. No allocation, no host synchronisation: every byte of
+ * scratch comes from `work`. flags: HC_FLAG_DIFF | HC_FLAG_ADAPT. The return value reports
+ * argument / launch errors only (and HC_ERR_WIDTH / _MATRIX_SIZE / _DIMS, decided on the host).
+ *
+ * The encoder codes every segment into a slot of hc_compress_bound(segment) bytes inside `work`
+ * and then gathers the slots into `out`: the slots are bound-sized, not guessed and retried, so
+ * the work bound is about 6x the input (plus the adaptive batch workspace for -a). */
+uint64_t hc_seg_compress_work_bound(uint64_t in_len, uint64_t seg_bytes, int use_adapt, uint64_t width);
+int hc_seg_compress_dev(const uint8_t *in, uint64_t in_len, uint32_t flags, uint64_t width, uint64_t seg_bytes,
+                        uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status,
+                        void *work, uint64_t work_bytes, void *stream);
+/* The decoder needs the header on the host (hc_seg_info of the first 48 bytes) to size its
+ * launches; the device bytes are checked against it. Segments decode in place into `out`. The
+ * buffer behind `in` must be readable up to in_len rounded up to a multiple of 4. */
+uint64_t hc_seg_decompress_work_bound(const hc_seg_info_t *info, uint64_t in_len);
+int hc_seg_decompress_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info,
+                          uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status,
+                          uint64_t *bad_segment, void *work, uint64_t work_bytes, void *stream);
 
 /* Allocation caches. The single-buffer API keeps device scratch between calls (per device,
  * at most 1 GiB each) and the host-buffer batch API keeps its pipeline buffers (per device;

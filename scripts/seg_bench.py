@@ -1,0 +1,156 @@
+#!/usr/bin/env python3
+"""Segmented container against whole-file coding on one large input.
+
+The input is the synthetic 4096x4096 photo (hc.synth_batch, width 4096) in -m, -a -m and -a.
+Each mode is coded through hc_seg_compress / hc_seg_decompress at 16, 64 and 256 KiB segments
+and through hc_compress / hc_decompress (one stream, one wavefront) in the same process; every
+call is a synchronous host-buffer call, timed with the host clock around it (copies included
+on both sides), median of the repeats after warm-up. Prints one JSON line.
+
+  scripts/seg_bench.py                       the sweep
+  scripts/seg_bench.py --trace-run           a few segmented calls only, to be run under
+                                             `rocprofv3 --kernel-trace --stats -- python ...`
+  scripts/seg_bench.py --glue-from STATS.csv adds the glue kernels' share of device time, read
+                                             from that run's *_kernel_stats.csv
+"""
+import argparse
+import csv
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "huffman-codec_amd", "python"))
+
+import hcodec as hc  # noqa: E402
+
+SIDE = 4096
+MODES = {"-m": (1, 0), "-a -m": (1, 1), "-a": (0, 1)}
+SIZES = (16384, 65536, 262144)
+GLUE = ("seg_plan_kernel", "seg_seal_kernel", "seg_gather_kernel", "seg_open_kernel", "seg_close_kernel")
+
+
+def photo():
+    import torch
+    n = SIDE * SIDE
+    raw = torch.empty(n, dtype=torch.uint8, device="cuda")
+    hc.synth_batch("photo", 0, 1, SIDE, SIDE, raw, n)
+    torch.cuda.synchronize()
+    return raw.cpu().numpy().tobytes()
+
+
+class Buffers:
+    """host buffers allocated once, so that a timed call is the library call alone"""
+
+    def __init__(self, raw):
+        self.L = hc.lib()
+        self.raw = raw
+        self.src = ctypes.cast(ctypes.c_char_p(raw), ctypes.c_void_p)
+        self.cap = max(int(self.L.hc_seg_compress_bound(len(raw), 16384, 0, SIDE)),
+                       int(self.L.hc_seg_compress_bound(len(raw), 16384, 1, SIDE)),
+                       hc.compress_bound(len(raw), True))
+        self.enc = ctypes.create_string_buffer(self.cap)
+        self.dec = ctypes.create_string_buffer(len(raw))
+        self.n = ctypes.c_uint64(0)
+
+    def p(self, b):
+        return ctypes.cast(b, ctypes.c_void_p)
+
+    def seg_encode(self, diff, adapt, seg):
+        rc = self.L.hc_seg_compress(self.src, len(self.raw), diff, adapt, SIDE, seg, self.p(self.enc), self.cap,
+                                    ctypes.byref(self.n))
+        assert rc == 0, rc
+        return self.n.value
+
+    def seg_decode(self, enc_len):
+        rc = self.L.hc_seg_decompress(self.p(self.enc), enc_len, self.p(self.dec), len(self.raw), ctypes.byref(self.n),
+                                      None)
+        assert rc == 0 and self.n.value == len(self.raw), rc
+
+    def whole_encode(self, diff, adapt):
+        rc = self.L.hc_compress(self.src, len(self.raw), diff, adapt, SIDE, self.p(self.enc), self.cap,
+                                ctypes.byref(self.n))
+        assert rc == 0, rc
+        return self.n.value
+
+    def whole_decode(self, enc_len):
+        rc = self.L.hc_decompress(self.p(self.enc), enc_len, self.p(self.dec), len(self.raw), ctypes.byref(self.n))
+        assert rc == 0 and self.n.value == len(self.raw), rc
+
+    def exact(self):
+        return self.dec.raw == self.raw
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return round(statistics.median(ts), 3), round(min(ts), 3), round(max(ts), 3)
+
+
+def glue_share(path):
+    glue = total = 0
+    per = {}
+    with open(path, newline="") as f:
+        for row in csv.DictReader(f):
+            ns = int(float(row["TotalDurationNs"]))
+            total += ns
+            for g in GLUE:
+                if g in row["Name"]:
+                    glue += ns
+                    per[g] = per.get(g, 0) + ns
+    return {"device_ms": round(total / 1e6, 3), "glue_ms": round(glue / 1e6, 3),
+            "glue_share": round(glue / total, 5) if total else None,
+            "glue_kernels_ms": {k: round(v / 1e6, 4) for k, v in per.items()}}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--trace-run", action="store_true")
+    ap.add_argument("--glue-from")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--whole-reps", type=int, default=2)
+    a = ap.parse_args()
+    if not hc.device_ok():
+        sys.exit("seg_bench.py needs a gfx950 device: " + hc.device_info())
+    b = Buffers(photo())
+    if a.trace_run:
+        for diff, adapt in MODES.values():
+            for _ in range(3):
+                b.seg_decode(b.seg_encode(diff, adapt, 65536))
+            assert b.exact()
+        return
+    res = {"input": f"synthetic photo {SIDE}x{SIDE} ({len(b.raw)} bytes)", "timing":
+           "host clock around each synchronous host-buffer call (copies included), median [min, max] ms",
+           "modes": {}}
+    for name, (diff, adapt) in MODES.items():
+        n = b.whole_encode(diff, adapt)
+        enc = timed(lambda: b.whole_encode(diff, adapt), 0, a.whole_reps)
+        dec = timed(lambda: b.whole_decode(n), 1, a.whole_reps)
+        assert b.exact()
+        m = {"whole": {"bytes": n, "encode_ms": enc, "decode_ms": dec}, "segmented": {}}
+        for seg in SIZES:
+            k = b.seg_encode(diff, adapt, seg)
+            e = timed(lambda: b.seg_encode(diff, adapt, seg), 2, a.reps)
+            b.dec = ctypes.create_string_buffer(len(b.raw))
+            d = timed(lambda: b.seg_decode(k), 2, a.reps)
+            assert b.exact()
+            m["segmented"][str(seg)] = {
+                "bytes": k, "size_ratio": round(k / n, 5), "segments": hc.seg_count(len(b.raw), seg, adapt, SIDE),
+                "encode_ms": e, "decode_ms": d,
+                "encode_speedup": round(enc[0] / e[0], 1), "decode_speedup": round(dec[0] / d[0], 1)}
+        res["modes"][name] = m
+    if a.glue_from:
+        res["glue"] = glue_share(a.glue_from)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
