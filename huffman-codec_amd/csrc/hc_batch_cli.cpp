@@ -3,7 +3,7 @@
 // process, main.cpp:202-220). Each output is byte-identical to what `huffman-codec` (and the
 // reference) writes for that file alone.
 //
-//   huffman-codec-batch [-c | -d] [-m] [-a [-w WIDTH]] [-s BYTES] [-o OUTDIR] [-j THREADS] FILE...
+//   huffman-codec-batch [-c | -d] [-m] [-a [-w WIDTH]] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...
 //
 // Compression writes FILE.huf, decompression FILE without its .huf suffix (else FILE.out);
 // with -o into OUTDIR under the same base name. Files are read and written by a pool of
@@ -13,9 +13,10 @@
 // "FILE: <the reference's message>"; the exit code is the first failing status (0: all ok).
 //
 // -s BYTES with -c writes every FILE.huf as a segmented container (HCSEG1, hcodec.h) of BYTES-byte
-// segments (0: the default size), one hc_seg_compress call per file. -d tells containers from
-// plain streams by their first 8 bytes and sends them through hc_seg_decompress_alloc; a failing
-// segment reports "FILE: segment K: <message>".
+// segments (0: the default size), one hc_seg_compress2 call per file; -k (only with -s) adds a
+// CRC-32 per segment. -d tells containers from plain streams by their first 8 bytes and sends them
+// through hc_seg_decompress_alloc, which verifies the checksums of a container that has them; a
+// failing segment reports "FILE: segment K: <message>".
 #include <unistd.h>
 
 #include <algorithm>
@@ -36,8 +37,8 @@ namespace {
 
 const char *const kHelp =
     "USAGE:\n"
-    "  huffman-codec-batch [-cm] [-s BYTES] [-o OUTDIR] [-j THREADS] FILE...\n"
-    "  huffman-codec-batch [-cm] -a [-w WIDTH] [-s BYTES] [-o OUTDIR] [-j THREADS] FILE...\n"
+    "  huffman-codec-batch [-cm] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
+    "  huffman-codec-batch [-cm] -a [-w WIDTH] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch -d [-o OUTDIR] [-j THREADS] FILE... | -h\n"
     "\n"
     "OPTION:\n"
@@ -46,6 +47,7 @@ const char *const kHelp =
     "  -a     use adaptive block RLE (default: RLE)\n"
     "  -w     width of 2D data (default: 512)\n"
     "  -s     write segmented containers of BYTES-byte segments (0: 65536)\n"
+    "  -k     with -s: store a CRC-32 of every segment, verified by -d\n"
     "  -o     output directory (default: next to each input)\n"
     "  -j     file I/O threads (default: 8)\n"
     "  -h     show this help\n"
@@ -83,13 +85,13 @@ void parallel(size_t n, unsigned threads, F &&f)
 
 int main(int argc, char *argv[])
 {
-    bool compress = true, use_diff = false, use_adapt = false, segmented = false;
+    bool compress = true, use_diff = false, use_adapt = false, segmented = false, check = false;
     uint64_t seg_bytes = 0;
     std::string dir;
     uint64_t width = 512;
     unsigned threads = 8;
     int opt;
-    while ((opt = getopt(argc, argv, ":cdmaw:s:o:j:h")) != -1) {
+    while ((opt = getopt(argc, argv, ":cdmaw:s:ko:j:h")) != -1) {
         switch (opt) {
         case 'c': compress = true; break;
         case 'd': compress = false; break;
@@ -100,12 +102,17 @@ int main(int argc, char *argv[])
             segmented = true;
             seg_bytes = std::stoull(optarg);
             break;
+        case 'k': check = true; break;
         case 'o': dir = optarg; break;
         case 'j': threads = (unsigned)std::stoul(optarg); break;
         case 'h': std::cout << kHelp; return 0;
         case ':': std::cerr << "ERROR: missing additional argument\n"; return 1;
         case '?': std::cerr << "ERROR: unrecognized option used\n"; return 2;
         }
+    }
+    if (check && !(compress && segmented)) {  // a checksum has nowhere to go but a container's index
+        std::cerr << "ERROR: unrecognized option used\n";
+        return 2;
     }
     std::vector<std::string> files(argv + optind, argv + argc);
     if (files.empty()) {
@@ -132,10 +139,12 @@ int main(int argc, char *argv[])
     if (compress && segmented) {  // one container per file, file after file
         for (size_t i = 0; i < n; ++i) {
             if (status[i]) continue;
-            out[i].resize(hc_seg_compress_bound(in[i].size(), seg_bytes, use_adapt, width));
+            const uint32_t fl = (use_diff ? HC_FLAG_DIFF : 0u) | (use_adapt ? HC_FLAG_ADAPT : 0u) |
+                                (check ? HC_SEG_CHECK_CRC32 : 0u);
+            out[i].resize(hc_seg_compress_bound2(in[i].size(), seg_bytes, fl, width));
             uint64_t len = 0;
-            status[i] = hc_seg_compress(in[i].data(), in[i].size(), use_diff, use_adapt, width, seg_bytes,
-                                        out[i].data(), out[i].size(), &len);
+            status[i] = hc_seg_compress2(in[i].data(), in[i].size(), fl, width, seg_bytes, out[i].data(),
+                                         out[i].size(), &len);
             out[i].resize(status[i] ? 0 : len);
         }
     } else if (compress) {  // -a: one matrix of width `width` per file

@@ -53,6 +53,18 @@ hipError_t adapt_decode_batch(const Batch &b, void *work, uint64_t work_bytes, h
 uint64_t adapt_encode_work_bound(uint64_t total_in, uint32_t n);
 uint64_t adapt_decode_work_bound(uint64_t total_in, uint64_t total_out, uint32_t n);
 
+// CRC-32 of n byte ranges in[offs[i] .. +lens[i]) into crc[i] (hc_crc.hip), asynchronous on st.
+// With a gate (the segmented decoder's; all three pointers or none) nothing at all is read when
+// ctl[0] != 0, and range i is skipped, crc[i] left alone, unless status[i] == 0 and
+// got_lens[i] == lens[i].
+struct CrcGate {
+    const uint64_t *ctl;
+    const int32_t *status;
+    const uint64_t *got_lens;
+};
+hipError_t launch_crc32(const uint8_t *in, const uint64_t *offs, const uint64_t *lens, uint64_t n, uint32_t *crc,
+                        const CrcGate &gate, hipStream_t st);
+
 // frees the host-batch pipeline slots' cached buffers (hc_release_cached; slots in use by a
 // running call are left alone)
 void pipe_release();

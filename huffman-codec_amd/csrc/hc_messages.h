@@ -22,6 +22,7 @@ inline const char *hc_status_message(int st)
     case HC_ERR_UNSUPPORTED: return "ERROR: stream exceeds the device coder's limits\n";
     case HC_ERR_SEG_HEADER: return "ERROR: invalid segmented container header or index\n";
     case HC_ERR_SEG_SIZE: return "ERROR: segment does not decode to its length\n";
+    case HC_ERR_SEG_CHECK: return "ERROR: segment checksum mismatch\n";
     case HC_ERR_DEVICE: return "ERROR: no usable gfx950 GPU (HIP runtime error)\n";
     default: return "ERROR: codec failure\n";
     }

@@ -6,6 +6,7 @@
 // buffer into a batch and back:
 //
 //   encode  seg_plan    per-segment in_offs / in_lens / widths and a bound-sized output slot
+//           <checked containers: CRC-32 of every segment's raw bytes (hc_crc.hip), into work>
 //           <encode launch over the n segments>
 //           seg_seal    one workgroup: scan of align16(enc_len) with a carried prefix, first
 //                       failing segment, capacity check, header and index
@@ -13,7 +14,9 @@
 //   decode  seg_open    one workgroup: header against the caller's host copy, index scan
 //                       (overflow-safe), segment arrays pointing straight into the output
 //           <decode launch: segments decode in place>
-//           seg_close   status, bad_segment, out_len
+//           <checked containers: CRC-32 of every cleanly decoded segment, in place in out>
+//           seg_close   status (a checksum that differs from the index fails its segment),
+//                       bad_segment, out_len
 //
 // Every launch is asynchronous on the caller's stream; no allocation, no host synchronisation,
 // no host read of device memory in the device entry points. A container-level error zeroes
@@ -40,6 +43,11 @@ const uint8_t kMagic[8] = {0x48, 0x43, 0x53, 0x45, 0x47, 0x31, 0x00, 0xFF};
 
 __host__ __device__ inline uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
 __host__ __device__ inline uint64_t sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
+
+constexpr uint32_t kSegFlags = HC_FLAG_DIFF | HC_FLAG_ADAPT | HC_SEG_CHECK_CRC32;
+// header and index: 8 bytes of enc_len per segment, and 4 of crc in a checked container
+inline bool checked(uint32_t flags) { return (flags & HC_SEG_CHECK_CRC32) != 0; }
+__host__ __device__ inline uint64_t index_end(uint64_t n, bool check) { return 48 + (check ? 12 : 8) * n; }
 
 // The cut rule: segment k is raw bytes [k full, k full + (k == n - 1 ? last : full)). n == 0:
 // invalid arguments. No product here overflows: every one is at most raw.
@@ -82,12 +90,12 @@ Cuts seg_cuts(uint64_t raw, uint64_t seg, bool adapt, uint64_t width)
 bool info_ok(const hc_seg_info_t &f, uint64_t in_len, Cuts &c)
 {
     if (in_len < 48) return false;
-    if (f.flags & ~(uint32_t)(HC_FLAG_DIFF | HC_FLAG_ADAPT)) return false;
+    if (f.flags & ~kSegFlags) return false;
     const bool adapt = (f.flags & HC_FLAG_ADAPT) != 0;
     if (!adapt && f.width != 0) return false;
     c = seg_cuts(f.raw_len, f.seg_bytes, adapt, f.width);
     if (c.n == 0 || c.n != f.n_segments) return false;
-    if (c.n > (in_len - 48) / 8) return false;  // 48 + 8 n <= in_len
+    if (c.n > (in_len - 48) / (checked(f.flags) ? 12 : 8)) return false;  // 48 + 8 n (checked: 12 n) <= in_len
     // at most 8 symbols per payload byte, and 4 symbols expand to at most 258 bytes
     if (in_len <= ~0ull / 520 && f.raw_len > 520 * in_len) return false;
     return true;
@@ -108,7 +116,7 @@ Header make_header(uint32_t flags, uint64_t raw_len, uint64_t seg_bytes, uint64_
 {
     Header h;
     h.w[0] = get64(kMagic);
-    h.w[1] = flags & 255u;
+    h.w[1] = flags & 0xFFFFu;  // byte 8 the flags, byte 9 the check kind
     h.w[2] = raw_len;
     h.w[3] = seg_bytes;
     h.w[4] = width;
@@ -122,12 +130,13 @@ Header make_header(uint32_t flags, uint64_t raw_len, uint64_t seg_bytes, uint64_
 struct EncWs {
     uint64_t *in_offs, *in_lens, *widths, *out_offs, *out_caps, *out_lens, *dst_offs;
     int32_t *status;
+    uint32_t *crc;   // checked containers: the segments' CRC-32 (otherwise no bytes)
     uint64_t *ctl;   // [0] 1: sealed, the gather may copy
     uint8_t *slots;  // the segments' bound-sized output slots
     void *awork;     // the adaptive batch workspace
     uint64_t awork_bytes, total;
 };
-EncWs carve_enc(void *work, uint64_t n, uint64_t slot_bytes, uint64_t awork_bytes)
+EncWs carve_enc(void *work, uint64_t n, uint64_t slot_bytes, uint64_t awork_bytes, bool check)
 {
     EncWs w;
     uint8_t *p = static_cast<uint8_t *>(work);
@@ -145,6 +154,7 @@ EncWs carve_enc(void *work, uint64_t n, uint64_t slot_bytes, uint64_t awork_byte
     w.out_lens = reinterpret_cast<uint64_t *>(take(8 * n));
     w.dst_offs = reinterpret_cast<uint64_t *>(take(8 * n));
     w.status = reinterpret_cast<int32_t *>(take(4 * n));
+    w.crc = reinterpret_cast<uint32_t *>(take(check ? 4 * n : 0));
     w.ctl = reinterpret_cast<uint64_t *>(take(16));
     w.slots = take(slot_bytes);
     w.awork = take(awork_bytes);
@@ -156,11 +166,12 @@ EncWs carve_enc(void *work, uint64_t n, uint64_t slot_bytes, uint64_t awork_byte
 struct DecWs {
     uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;
     int32_t *status;
+    uint32_t *crc;  // checked containers: the decoded segments' CRC-32 (otherwise no bytes)
     uint64_t *ctl;  // [0] the container-level status (0, HC_ERR_SEG_HEADER, HC_ERR_CAPACITY)
     void *awork;
     uint64_t awork_bytes, total;
 };
-DecWs carve_dec(void *work, uint64_t n, uint64_t awork_bytes)
+DecWs carve_dec(void *work, uint64_t n, uint64_t awork_bytes, bool check)
 {
     DecWs w;
     uint8_t *p = static_cast<uint8_t *>(work);
@@ -176,6 +187,7 @@ DecWs carve_dec(void *work, uint64_t n, uint64_t awork_bytes)
     w.out_caps = reinterpret_cast<uint64_t *>(take(8 * n));
     w.out_lens = reinterpret_cast<uint64_t *>(take(8 * n));
     w.status = reinterpret_cast<int32_t *>(take(4 * n));
+    w.crc = reinterpret_cast<uint32_t *>(take(check ? 4 * n : 0));
     w.ctl = reinterpret_cast<uint64_t *>(take(16));
     w.awork = take(awork_bytes);
     w.awork_bytes = awork_bytes;
@@ -238,6 +250,7 @@ __global__ __launch_bounds__(256) void seg_plan_kernel(PlanArgs a)
 struct SealArgs {
     const uint64_t *enc_lens;
     const int32_t *seg_status;
+    const uint32_t *crc;  // null: an unchecked container
     uint64_t *dst_offs, *ctl;
     uint64_t n;
     uint8_t *out;
@@ -257,7 +270,8 @@ __global__ __launch_bounds__(kScan) void seg_seal_kernel(SealArgs a)
         s_end = 0;
     }
     __syncthreads();
-    uint64_t carry = align16(48 + 8 * a.n);  // where segment 0 starts
+    const uint64_t idx_end = index_end(a.n, a.crc != nullptr);
+    uint64_t carry = align16(idx_end);  // where segment 0 starts
     uint64_t bad = kNoSeg;
     for (uint64_t base = 0; base < a.n; base += kScan) {
         const uint64_t k = base + tid;
@@ -282,11 +296,15 @@ __global__ __launch_bounds__(kScan) void seg_seal_kernel(SealArgs a)
         a.ctl[0] = st == 0 ? 1 : 0;
     }
     if (st != 0) return;
-    // sealed: end <= out_cap, so the header, the index and its padding word lie inside out
+    // sealed: end <= out_cap, so the header, the index and its padding lie inside out
     uint64_t *o64 = reinterpret_cast<uint64_t *>(a.out);
+    uint32_t *o32 = reinterpret_cast<uint32_t *>(a.out);
     if (tid < 6) o64[tid] = a.hdr.w[tid];
-    if (tid == 6 && (a.n & 1u)) o64[6 + a.n] = 0;  // 48 + 8 n is 8 mod 16: pad up to segment 0
+    // the index ends on a multiple of 4: zero words up to segment 0
+    if (tid >= 8 && tid < 8 + (align16(idx_end) - idx_end) / 4) o32[idx_end / 4 + (tid - 8)] = 0;
     for (uint64_t k = tid; k < a.n; k += kScan) o64[6 + k] = a.enc_lens[k];
+    if (a.crc)
+        for (uint64_t k = tid; k < a.n; k += kScan) o32[12 + 2 * a.n + k] = a.crc[k];
 }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -336,11 +354,12 @@ struct OpenArgs {
     uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;
     int32_t *status;
     uint64_t *ctl;
+    bool check;
 };
 
-// The host has checked its copy of the header against in_len (48 + 8 n <= in_len among the rest);
-// here the device bytes must equal that copy, and the index must tile [align16(48 + 8 n), in_len)
-// exactly. enc_len entries are untrusted: the offsets add with saturation and every range is
+// The host has checked its copy of the header against in_len (48 + 8 n <= in_len among the rest;
+// 12 n in a checked container, whose crc words follow the lengths); here the device bytes must
+// equal that copy, and the index must tile [align16(48 + 8 n or 12 n), in_len) exactly. enc_len entries are untrusted: the offsets add with saturation and every range is
 // compared by subtraction, so a forged length cannot wrap into a valid offset.
 __global__ __launch_bounds__(kScan) void seg_open_kernel(OpenArgs a)
 {
@@ -352,7 +371,7 @@ __global__ __launch_bounds__(kScan) void seg_open_kernel(OpenArgs a)
     bool err = false;
     const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in);
     if (tid < 6 && i64[tid] != a.hdr.w[tid]) err = true;
-    uint64_t carry = align16(48 + 8 * a.n);
+    uint64_t carry = align16(index_end(a.n, a.check));
     for (uint64_t base = 0; base < a.n; base += kScan) {
         const uint64_t k = base + tid;
         const bool in = k < a.n;
@@ -386,6 +405,7 @@ __global__ __launch_bounds__(kScan) void seg_open_kernel(OpenArgs a)
 struct CloseArgs {
     const uint64_t *out_lens, *out_caps, *ctl;
     const int32_t *seg_status;
+    const uint32_t *crc, *want_crc;  // checked containers: of the decoded bytes, and the index's (else null)
     uint64_t n, raw_len;
     uint64_t *out_len, *bad_segment;
     int32_t *status;
@@ -399,10 +419,12 @@ __global__ __launch_bounds__(kScan) void seg_close_kernel(CloseArgs a)
     __syncthreads();
     const int32_t top = (int32_t)a.ctl[0];
     if (top == 0) {
-        // the lowest segment that failed, or decoded cleanly to another length than its cut
+        // the lowest segment that failed, decoded cleanly to another length than its cut, or to
+        // that length with another checksum (crc[k] is written exactly for those that reach it)
         uint64_t bad = kNoSeg;
         for (uint64_t k = tid; k < a.n && bad == kNoSeg; k += kScan)
-            if (a.seg_status[k] != 0 || a.out_lens[k] != a.out_caps[k]) bad = k;
+            if (a.seg_status[k] != 0 || a.out_lens[k] != a.out_caps[k] || (a.crc && a.crc[k] != a.want_crc[k]))
+                bad = k;
         if (bad != kNoSeg) atomicMin(&s_bad, (unsigned long long)bad);
     }
     __syncthreads();
@@ -413,8 +435,9 @@ __global__ __launch_bounds__(kScan) void seg_close_kernel(CloseArgs a)
     if (top == 0) {
         if (bad != kNoSeg) {
             st = a.seg_status[bad];
-            // 64: it wanted more room than its cut; 0: it decoded to fewer bytes
-            if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
+            // 64: it wanted more room than its cut; 0: it decoded to fewer bytes, or to the wrong ones
+            if (st == 0 && a.out_lens[bad] == a.out_caps[bad]) st = HC_ERR_SEG_CHECK;
+            else if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
         } else {
             len = a.raw_len;
         }
@@ -498,6 +521,40 @@ int seg_decompress_host(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64
     return HC_OK;
 }
 
+// hc_seg_compress / hc_seg_compress2 after their own argument checks
+int seg_compress_host(const uint8_t *in, uint64_t in_len, uint32_t flags, uint64_t width, uint64_t seg_bytes,
+                      uint8_t *out, uint64_t out_cap, uint64_t *out_len)
+{
+    if (seg_bytes & 15u) return HC_ERR_ARG;
+    const int use_adapt = (flags & HC_FLAG_ADAPT) ? 1 : 0;
+    const int hs = host_status(in_len, use_adapt, width);
+    if (hs) return hs;
+    if (!hc_device_ok()) return HC_ERR_DEVICE;
+    const uint64_t cap = hc_seg_compress_bound2(in_len, seg_bytes, flags, width);
+    const uint64_t wb = hc_seg_compress_work_bound2(in_len, seg_bytes, flags, width);
+    if (cap == 0 || wb == 0) return HC_ERR_ARG;
+    hipStream_t st = nullptr;
+    DevBuf din, dout, work, meta;
+    HC_CK(din.alloc(in_len + 16));
+    HC_CK(dout.alloc(cap));
+    HC_CK(work.alloc(wb));
+    HC_CK(meta.alloc(32));
+    if (in_len) HC_CK(hipMemcpyAsync(din.p, in, in_len, hipMemcpyHostToDevice, st));
+    uint64_t *m = meta.as<uint64_t>();
+    const int rc = hc_seg_compress_dev(din.as<uint8_t>(), in_len, flags, width, seg_bytes, dout.as<uint8_t>(), cap, m,
+                                       reinterpret_cast<int32_t *>(m + 1), work.p, wb, st);
+    if (rc) return rc;
+    uint64_t h[2] = {0, 0};
+    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    HC_CK(hipStreamSynchronize(st));
+    const int status = (int32_t)(uint32_t)h[1];
+    if (status) return status;
+    *out_len = h[0];
+    if (h[0] > out_cap) return HC_ERR_CAPACITY;
+    HC_CK(hipMemcpy(out, dout.p, h[0], hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -509,9 +566,14 @@ uint64_t hc_seg_count(uint64_t in_len, uint64_t seg_bytes, int use_adapt, uint64
 
 uint64_t hc_seg_compress_bound(uint64_t in_len, uint64_t seg_bytes, int use_adapt, uint64_t width)
 {
+    return hc_seg_compress_bound2(in_len, seg_bytes, use_adapt ? HC_FLAG_ADAPT : 0u, width);
+}
+
+uint64_t hc_seg_compress_bound2(uint64_t in_len, uint64_t seg_bytes, uint32_t flags, uint64_t width)
+{
     EncPlan p;
-    if (!enc_plan(in_len, seg_bytes, use_adapt, width, p)) return 0;
-    return align16(48 + 8 * p.c.n) + p.slot_bytes;
+    if ((flags & ~kSegFlags) || !enc_plan(in_len, seg_bytes, (flags & HC_FLAG_ADAPT) != 0, width, p)) return 0;
+    return align16(index_end(p.c.n, checked(flags))) + p.slot_bytes;
 }
 
 int hc_seg_info(const uint8_t *in, uint64_t in_len, hc_seg_info_t *info)
@@ -520,10 +582,11 @@ int hc_seg_info(const uint8_t *in, uint64_t in_len, hc_seg_info_t *info)
     memset(info, 0, sizeof(*info));
     if (!in || in_len < 48) return HC_ERR_SEG_HEADER;
     if (memcmp(in, kMagic, 8) != 0) return HC_ERR_SEG_HEADER;
-    for (int i = 9; i < 16; ++i)
+    if (in[9] > 1) return HC_ERR_SEG_HEADER;  // the check kind: none or CRC-32
+    for (int i = 10; i < 16; ++i)
         if (in[i]) return HC_ERR_SEG_HEADER;
     hc_seg_info_t f;
-    f.flags = in[8];
+    f.flags = in[8] | ((uint32_t)in[9] << 8);
     f.raw_len = get64(in + 16);
     f.seg_bytes = get64(in + 24);
     f.width = get64(in + 32);
@@ -540,9 +603,14 @@ uint64_t hc_seg_compress_work_bound(uint64_t in_len, uint64_t seg_bytes, int use
     // worst case every batch caller sizes by, and gathered afterwards: nothing is guessed and
     // retried. That bound is 6 bytes per symbol, so this is about 6x the input (8x with the
     // adaptive workspace), most of it never touched.
+    return hc_seg_compress_work_bound2(in_len, seg_bytes, use_adapt ? HC_FLAG_ADAPT : 0u, width);
+}
+
+uint64_t hc_seg_compress_work_bound2(uint64_t in_len, uint64_t seg_bytes, uint32_t flags, uint64_t width)
+{
     EncPlan p;
-    if (!enc_plan(in_len, seg_bytes, use_adapt, width, p)) return 0;
-    return carve_enc(nullptr, p.c.n, p.slot_bytes, p.awork_bytes).total;
+    if ((flags & ~kSegFlags) || !enc_plan(in_len, seg_bytes, (flags & HC_FLAG_ADAPT) != 0, width, p)) return 0;
+    return carve_enc(nullptr, p.c.n, p.slot_bytes, p.awork_bytes, checked(flags)).total;
 }
 
 int hc_seg_compress_dev(const uint8_t *in, uint64_t in_len, uint32_t flags, uint64_t width, uint64_t seg_bytes,
@@ -550,7 +618,7 @@ int hc_seg_compress_dev(const uint8_t *in, uint64_t in_len, uint32_t flags, uint
                         uint64_t work_bytes, void *stream)
 {
     if ((!in && in_len) || !out || !out_len || !status || !work) return HC_ERR_ARG;
-    if (flags & ~(uint32_t)(HC_FLAG_DIFF | HC_FLAG_ADAPT)) return HC_ERR_ARG;
+    if (flags & ~kSegFlags) return HC_ERR_ARG;
     if (seg_bytes & 15u) return HC_ERR_ARG;
     if (!aligned16(in) || !aligned16(out) || !aligned16(work)) return HC_ERR_ARG;
     const int use_adapt = (flags & HC_FLAG_ADAPT) ? 1 : 0;
@@ -559,7 +627,8 @@ int hc_seg_compress_dev(const uint8_t *in, uint64_t in_len, uint32_t flags, uint
     if (!seg_bytes) seg_bytes = HC_SEG_DEFAULT_BYTES;
     EncPlan p;
     if (!enc_plan(in_len, seg_bytes, use_adapt, width, p)) return HC_ERR_ARG;
-    const EncWs w = carve_enc(work, p.c.n, p.slot_bytes, p.awork_bytes);
+    const bool check = checked(flags);
+    const EncWs w = carve_enc(work, p.c.n, p.slot_bytes, p.awork_bytes, check);
     if (work_bytes < w.total) return HC_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint32_t n = (uint32_t)p.c.n;
@@ -570,9 +639,11 @@ int hc_seg_compress_dev(const uint8_t *in, uint64_t in_len, uint32_t flags, uint
     HC_CK(hipGetLastError());
     Batch b{in ? in : out, w.in_offs, w.in_lens, n, w.slots, w.out_offs, w.out_caps, w.out_lens, w.status,
             flags & HC_FLAG_DIFF};
+    // the raw bytes of every cut, before the diff model (an empty input has one empty segment: crc 0)
+    if (check) HC_CK(hc::launch_crc32(b.in, w.in_offs, w.in_lens, n, w.crc, hc::CrcGate{nullptr, nullptr, nullptr}, st));
     if (use_adapt) HC_CK(hc::adapt_encode_batch(b, w.widths, w.awork, w.awork_bytes, st));
     else HC_CK(hc::launch_encode(b, (flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
-    const SealArgs sa{w.out_lens, w.status, w.dst_offs, w.ctl, p.c.n, out, out_cap, out_len, status,
+    const SealArgs sa{w.out_lens, w.status, check ? w.crc : nullptr, w.dst_offs, w.ctl, p.c.n, out, out_cap, out_len, status,
                       make_header(flags, in_len, seg_bytes, use_adapt ? width : 0, p.c.n)};
     seg_seal_kernel<<<1, kScan, 0, st>>>(sa);
     seg_gather_kernel<<<n < 65536u ? n : 65536u, 256, 0, st>>>(w.slots, w.out_offs, w.out_lens, w.dst_offs, w.ctl,
@@ -588,7 +659,7 @@ uint64_t hc_seg_decompress_work_bound(const hc_seg_info_t *info, uint64_t in_len
     if (!info_ok(*info, in_len, c) || c.n > kMaxSegs) return 16;  // rejected without a workspace
     const uint64_t aw =
         (info->flags & HC_FLAG_ADAPT) ? hc::adapt_decode_work_bound(in_len, info->raw_len, (uint32_t)c.n) : 0;
-    return carve_dec(nullptr, c.n, aw).total;
+    return carve_dec(nullptr, c.n, aw, checked(info->flags)).total;
 }
 
 int hc_seg_decompress_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, uint8_t *out,
@@ -607,18 +678,23 @@ int hc_seg_decompress_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_
     if (c.n > kMaxSegs) return HC_ERR_ARG;
     const bool adapt = (info->flags & HC_FLAG_ADAPT) != 0;
     const uint32_t n = (uint32_t)c.n;
-    const DecWs w = carve_dec(work, c.n, adapt ? hc::adapt_decode_work_bound(in_len, info->raw_len, n) : 0);
+    const bool check = checked(info->flags);
+    const DecWs w = carve_dec(work, c.n, adapt ? hc::adapt_decode_work_bound(in_len, info->raw_len, n) : 0, check);
     if (work_bytes < w.total) return HC_ERR_ARG;
 
     const OpenArgs oa{in, in_len, make_header(info->flags, info->raw_len, info->seg_bytes, info->width, c.n),
                       c.n, c.full, c.last, info->raw_len, out_cap,
-                      w.in_offs, w.in_lens, w.out_offs, w.out_caps, w.out_lens, w.status, w.ctl};
+                      w.in_offs, w.in_lens, w.out_offs, w.out_caps, w.out_lens, w.status, w.ctl, check};
     seg_open_kernel<<<1, kScan, 0, st>>>(oa);
     HC_CK(hipGetLastError());
     Batch b{in, w.in_offs, w.in_lens, n, out, w.out_offs, w.out_caps, w.out_lens, w.status, 0};
     if (adapt) HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
     else HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
-    const CloseArgs ca{w.out_lens, w.out_caps, w.ctl, w.status, c.n, info->raw_len, out_len, bad_segment, status};
+    // segments that decoded cleanly to their cut's length, in place; none when the verdict is set
+    if (check) HC_CK(hc::launch_crc32(out, w.out_offs, w.out_caps, n, w.crc, hc::CrcGate{w.ctl, w.status, w.out_lens}, st));
+    const CloseArgs ca{w.out_lens, w.out_caps, w.ctl, w.status, check ? w.crc : nullptr,
+                       check ? reinterpret_cast<const uint32_t *>(in + 48 + 8 * c.n) : nullptr,
+                       c.n, info->raw_len, out_len, bad_segment, status};
     seg_close_kernel<<<1, kScan, 0, st>>>(ca);
     HC_CK(hipGetLastError());
     return HC_OK;
@@ -628,35 +704,16 @@ int hc_seg_compress(const uint8_t *in, uint64_t in_len, int use_diff, int use_ad
                     uint64_t seg_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len)
 {
     if ((!in && in_len) || !out_len || (!out && out_cap)) return HC_ERR_ARG;
-    if (seg_bytes & 15u) return HC_ERR_ARG;
-    const int hs = host_status(in_len, use_adapt, width);
-    if (hs) return hs;
-    if (!hc_device_ok()) return HC_ERR_DEVICE;
-    EncPlan p;
-    if (!enc_plan(in_len, seg_bytes, use_adapt, width, p)) return HC_ERR_ARG;
-    const uint64_t cap = align16(48 + 8 * p.c.n) + p.slot_bytes;
-    const uint64_t wb = hc_seg_compress_work_bound(in_len, seg_bytes, use_adapt, width);
-    hipStream_t st = nullptr;
-    DevBuf din, dout, work, meta;
-    HC_CK(din.alloc(in_len + 16));
-    HC_CK(dout.alloc(cap));
-    HC_CK(work.alloc(wb));
-    HC_CK(meta.alloc(32));
-    if (in_len) HC_CK(hipMemcpyAsync(din.p, in, in_len, hipMemcpyHostToDevice, st));
-    uint64_t *m = meta.as<uint64_t>();
     const uint32_t flags = (use_diff ? HC_FLAG_DIFF : 0u) | (use_adapt ? HC_FLAG_ADAPT : 0u);
-    const int rc = hc_seg_compress_dev(din.as<uint8_t>(), in_len, flags, width, seg_bytes, dout.as<uint8_t>(), cap, m,
-                                       reinterpret_cast<int32_t *>(m + 1), work.p, wb, st);
-    if (rc) return rc;
-    uint64_t h[2] = {0, 0};
-    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    HC_CK(hipStreamSynchronize(st));
-    const int status = (int32_t)(uint32_t)h[1];
-    if (status) return status;
-    *out_len = h[0];
-    if (h[0] > out_cap) return HC_ERR_CAPACITY;
-    HC_CK(hipMemcpy(out, dout.p, h[0], hipMemcpyDeviceToHost));
-    return HC_OK;
+    return seg_compress_host(in, in_len, flags, width, seg_bytes, out, out_cap, out_len);
+}
+
+int hc_seg_compress2(const uint8_t *in, uint64_t in_len, uint32_t flags, uint64_t width, uint64_t seg_bytes,
+                     uint8_t *out, uint64_t out_cap, uint64_t *out_len)
+{
+    if ((!in && in_len) || !out_len || (!out && out_cap)) return HC_ERR_ARG;
+    if (flags & ~kSegFlags) return HC_ERR_ARG;
+    return seg_compress_host(in, in_len, flags, width, seg_bytes, out, out_cap, out_len);
 }
 
 int hc_seg_decompress(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap, uint64_t *out_len,

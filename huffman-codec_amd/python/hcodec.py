@@ -38,9 +38,11 @@ HC_ERR_SEG_HEADER = 68
 HC_ERR_SEG_SIZE = 69
 HC_ERR_DEVICE = 70
 HC_ERR_ARG = 71
+HC_ERR_SEG_CHECK = 72
 
 HC_FLAG_DIFF = 0x80
 HC_FLAG_ADAPT = 0x40
+HC_SEG_CHECK_CRC32 = 0x100   # segmented encoders: a CRC-32 per segment; SegInfo.flags of a checked container
 HC_SEG_DEFAULT_BYTES = 65536
 NO_SEGMENT = 2**64 - 1   # bad_segment when no segment failed
 
@@ -127,6 +129,11 @@ def _load(path):
     for f in (L.hc_seg_count, L.hc_seg_compress_bound, L.hc_seg_compress_work_bound):
         f.argtypes = [u64, u64, ctypes.c_int, u64]
         f.restype = u64
+    for f in (L.hc_seg_compress_bound2, L.hc_seg_compress_work_bound2):
+        f.argtypes = [u64, u64, ctypes.c_uint32, u64]
+        f.restype = u64
+    L.hc_seg_compress2.argtypes = [u8p, u64, ctypes.c_uint32, u64, u64, u8p, u64, ctypes.POINTER(u64)]
+    L.hc_crc32_batch.argtypes = [vp, vp, vp, ctypes.c_uint32, vp, vp]
     L.hc_seg_info.argtypes = [u8p, u64, ctypes.POINTER(SegInfo)]
     L.hc_seg_compress.argtypes = [u8p, u64, ctypes.c_int, ctypes.c_int, u64, u64, u8p, u64, ctypes.POINTER(u64)]
     L.hc_seg_decompress.argtypes = [u8p, u64, u8p, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
@@ -312,8 +319,13 @@ def seg_count(n, seg_bytes=0, use_adapt=False, width=512):
     return int(lib().hc_seg_count(n, seg_bytes, int(bool(use_adapt)), width))
 
 
-def seg_compress_bound(n, seg_bytes=0, use_adapt=False, width=512):
-    return int(lib().hc_seg_compress_bound(n, seg_bytes, int(bool(use_adapt)), width))
+def _seg_flags(use_diff, use_adapt, check):
+    return (HC_FLAG_DIFF if use_diff else 0) | (HC_FLAG_ADAPT if use_adapt else 0) | (HC_SEG_CHECK_CRC32 if check else 0)
+
+
+def seg_compress_bound(n, seg_bytes=0, use_adapt=False, width=512, check=False):
+    """hc_seg_compress_bound2: the worst-case container size (check: with a CRC-32 per segment)"""
+    return int(lib().hc_seg_compress_bound2(n, seg_bytes, _seg_flags(False, use_adapt, check), width))
 
 
 def seg_info(data):
@@ -324,17 +336,18 @@ def seg_info(data):
     return st, (info if st == 0 else None)
 
 
-def seg_compress(data, use_diff=False, use_adapt=False, width=512, seg_bytes=0, cap=None):
-    """hc_seg_compress: (status, HCSEG1 container) of one input coded as parallel segments.
-    cap: the output capacity (default: hc_seg_compress_bound)."""
+def seg_compress(data, use_diff=False, use_adapt=False, width=512, seg_bytes=0, cap=None, check=False):
+    """hc_seg_compress2: (status, HCSEG1 container) of one input coded as parallel segments.
+    cap: the output capacity (default: hc_seg_compress_bound2). check: store a CRC-32 of every
+    segment's raw bytes in the index; the decoders verify it."""
     b, p = _buf(data)
+    flags = _seg_flags(use_diff, use_adapt, check)
     if cap is None:
-        cap = lib().hc_seg_compress_bound(len(b), seg_bytes if seg_bytes % 16 == 0 else 0,
-                                          int(bool(use_adapt)), width)
+        cap = lib().hc_seg_compress_bound2(len(b), seg_bytes if seg_bytes % 16 == 0 else 0, flags, width)
     out = ctypes.create_string_buffer(max(int(cap), 1))
     n = ctypes.c_uint64(0)
-    st = lib().hc_seg_compress(p, len(b), int(bool(use_diff)), int(bool(use_adapt)), width, seg_bytes,
-                               ctypes.cast(out, ctypes.c_void_p), cap, ctypes.byref(n))
+    st = lib().hc_seg_compress2(p, len(b), flags, width, seg_bytes, ctypes.cast(out, ctypes.c_void_p), cap,
+                                ctypes.byref(n))
     return st, (out.raw[:n.value] if st == 0 else b"")
 
 
@@ -378,16 +391,17 @@ def _check_seg(inp, out, out_len, status, bad_segment):
 
 
 def seg_compress_dev(inp, out, out_len, status, use_diff=False, use_adapt=False, width=512, seg_bytes=0,
-                     stream=None, work=None, out_cap=None):
+                     stream=None, work=None, out_cap=None, check=False):
     """hc_seg_compress_dev on CUDA tensors: the whole of `inp` (uint8) into one container in `out`
     (capacity out_cap, default all of it); out_len (int64[1]) and status (int32[1]) are device
-    results, asynchronous on `stream`. The workspace is allocated here unless given. Returns it."""
+    results, asynchronous on `stream`. check: a checked container (a CRC-32 per segment). The
+    workspace is allocated here unless given. Returns it."""
     _check_seg(inp, out, out_len, status, None)
     cap = out.numel() if out_cap is None else int(out_cap)
     if cap > out.numel():
         raise ValueError(f"out_cap {cap} exceeds the {out.numel()}-byte output tensor")
-    flags = (HC_FLAG_DIFF if use_diff else 0) | (HC_FLAG_ADAPT if use_adapt else 0)
-    need = int(lib().hc_seg_compress_work_bound(inp.numel(), seg_bytes, int(bool(use_adapt)), width))
+    flags = _seg_flags(use_diff, use_adapt, check)
+    need = int(lib().hc_seg_compress_work_bound2(inp.numel(), seg_bytes, flags, width))
     if work is None:
         work = _work(need, inp.device)
     _check_work(work, inp.device, need)
@@ -425,6 +439,23 @@ def seg_decompress_dev(inp, out, out_len, status, bad_segment=None, info=None, s
     if rc:
         raise HCodecError(f"hc_seg_decompress_dev failed: {rc}")
     return work
+
+
+def crc32_batch(inp, in_offs, lens, crc, stream=None):
+    """hc_crc32_batch on CUDA tensors: crc[i] (int32 or uint32 storage, one per range) =
+    zlib.crc32(inp[in_offs[i]:+lens[i]]); any alignment, any length, asynchronous on `stream`."""
+    import torch
+    n = in_offs.numel()
+    for name, t, dts in (("in", inp, (torch.uint8,)), ("in_offs", in_offs, (torch.int64,)), ("lens", lens, (torch.int64,)),
+                         ("crc", crc, (torch.int32, getattr(torch, "uint32", torch.int32)))):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == inp.device and t.dtype in dts
+                and t.is_contiguous()):
+            raise ValueError(f"{name}: expected a contiguous {dts[0]} CUDA tensor on {inp.device}")
+    if lens.numel() != n or crc.numel() != n:
+        raise ValueError("in_offs, lens and crc must have one entry per range")
+    rc = lib().hc_crc32_batch(_dp(inp), _dp(in_offs), _dp(lens), n, _dp(crc), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_crc32_batch failed: {rc}")
 
 
 def pack_batch(inp, in_offs, lens, out, out_offs, stream=None):

@@ -44,7 +44,9 @@ enum hc_status {
     HC_ERR_SEG_HEADER = 68,   /* segmented container: bad header, index or length            */
     HC_ERR_SEG_SIZE = 69,     /* segmented container: a segment decodes to another length    */
     HC_ERR_DEVICE = 70,       /* HIP runtime error / no gfx950 device                        */
-    HC_ERR_ARG = 71           /* null pointer, misaligned device buffer, bad flag            */
+    HC_ERR_ARG = 71,          /* null pointer, misaligned device buffer, bad flag            */
+    HC_ERR_SEG_CHECK = 72     /* segmented container: a segment decodes to its cut's length,
+                                 but its checksum differs from the index                    */
 };
 
 /* Flags byte of the outer header (headers.cpp:118-122): bit 7 diff model, bit 6 adaptive RLE */
@@ -188,12 +190,16 @@ int hc_pack_batch(const uint8_t *in, const uint64_t *in_offs, const uint64_t *le
  *
  *   0   8   magic  48 43 53 45 47 31 00 FF ("HCSEG1\0\xFF")
  *   8   1   flags  HC_FLAG_DIFF | HC_FLAG_ADAPT, other bits 0
- *   9   7   zero
+ *   9   1   check  0 none, 1 CRC-32 per segment; any other value is invalid
+ *   10  6   zero
  *   16  8   raw_len     decoded bytes in total
  *   24  8   seg_bytes   the segment size given to the encoder (multiple of 16, >= 16)
  *   32  8   width       adaptive: matrix width; otherwise 0
  *   40  8   n_segments  >= 1
  *   48  8n  enc_len[k]  byte length of segment k's stream
+ *   check == 1 only: 4n  crc[k], uint32: the CRC-32 of segment k's raw bytes (the bytes of its
+ *               cut, before the diff model) as zlib / IEEE 802.3 define it: reflected polynomial
+ *               0xEDB88320, init and final xor 0xFFFFFFFF; of an empty segment, 0
  *   then the segments in order, each at the next multiple of 16 (padding bytes 0); the
  *   container ends with the last byte of the last segment.
  *
@@ -203,8 +209,18 @@ int hc_pack_batch(const uint8_t *in, const uint64_t *in_offs, const uint64_t *le
  * adaptive, the segments are bands of rows = max(8, floor(seg_bytes / width) & ~3) rows, each
  * coded as its own width x rows matrix, and a band that would leave fewer than 8 rows takes
  * those too.
+ *
+ * The check is opt-in (HC_SEG_CHECK_CRC32 to the encoders named below): a damaged FGK stream is
+ * often still a valid one that decodes to the right length and the wrong bytes. With check == 0
+ * the container is what it always was. The decoders take both kinds; in a checked one, a segment
+ * that decodes cleanly to its cut's length with another CRC-32 than the index's fails with
+ * HC_ERR_SEG_CHECK, by the same lowest-failing-segment rule as every other segment error.
  * ------------------------------------------------------------------------------------- */
 #define HC_SEG_DEFAULT_BYTES 65536u
+/* Asks the segmented encoders for a checked container. Valid only in the `flags` of
+ * hc_seg_compress_bound2, hc_seg_compress_work_bound2, hc_seg_compress2 and hc_seg_compress_dev;
+ * hc_seg_info_t.flags reports header byte 9 in bits 8-15, so a checked container has it set. */
+#define HC_SEG_CHECK_CRC32 0x100u
 typedef struct hc_seg_info_t {
     uint64_t raw_len, seg_bytes, width, n_segments;
     uint32_t flags;
@@ -216,8 +232,12 @@ typedef struct hc_seg_info_t {
 uint64_t hc_seg_count(uint64_t in_len, uint64_t seg_bytes, int use_adapt, uint64_t width);
 /* Worst-case container size (0 when invalid). */
 uint64_t hc_seg_compress_bound(uint64_t in_len, uint64_t seg_bytes, int use_adapt, uint64_t width);
+/* The same with flags = HC_FLAG_DIFF | HC_FLAG_ADAPT | HC_SEG_CHECK_CRC32 (other bits: 0 is
+ * returned); without the check bit, hc_seg_compress_bound's value. */
+uint64_t hc_seg_compress_bound2(uint64_t in_len, uint64_t seg_bytes, uint32_t flags, uint64_t width);
 /* Host only, no device: parses and checks the 48 header bytes against in_len (every header rule,
- * 48 + 8 n <= in_len, raw_len <= 520 in_len). HC_OK and *info, or HC_ERR_SEG_HEADER. */
+ * 48 + 8 n <= in_len (checked: 48 + 12 n), raw_len <= 520 in_len). HC_OK and *info, or
+ * HC_ERR_SEG_HEADER. */
 int hc_seg_info(const uint8_t *in, uint64_t in_len, hc_seg_info_t *info);
 
 /* Host buffers, synchronous. seg_bytes 0: HC_SEG_DEFAULT_BYTES. Returns HC_ERR_ARG (null
@@ -225,9 +245,14 @@ int hc_seg_info(const uint8_t *in, uint64_t in_len, hc_seg_info_t *info);
  * as hc_compress, HC_ERR_DEVICE, HC_ERR_CAPACITY (*out_len = needed). */
 int hc_seg_compress(const uint8_t *in, uint64_t in_len, int use_diff, int use_adapt, uint64_t width,
                     uint64_t seg_bytes, uint8_t *out, uint64_t out_cap, uint64_t *out_len);
+/* The same with flags = HC_FLAG_DIFF | HC_FLAG_ADAPT | HC_SEG_CHECK_CRC32 (any other bit:
+ * HC_ERR_ARG): with the check bit, a checked container. */
+int hc_seg_compress2(const uint8_t *in, uint64_t in_len, uint32_t flags, uint64_t width, uint64_t seg_bytes,
+                     uint8_t *out, uint64_t out_cap, uint64_t *out_len);
 /* HC_ERR_SEG_HEADER (bad container; *out_len = 0), HC_ERR_CAPACITY (*out_len = raw_len), the
  * status of the lowest failing segment with *bad_segment its index (a segment that wants
- * another length than its cut: HC_ERR_SEG_SIZE), or HC_OK. *bad_segment (may be NULL) is
+ * another length than its cut: HC_ERR_SEG_SIZE; in a checked container, one with the right
+ * length and another checksum: HC_ERR_SEG_CHECK), or HC_OK. *bad_segment (may be NULL) is
  * UINT64_MAX unless a segment failed. */
 int hc_seg_decompress(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap,
                       uint64_t *out_len, uint64_t *bad_segment);
@@ -237,23 +262,33 @@ int hc_seg_decompress_alloc(const uint8_t *in, uint64_t in_len, uint8_t **out, u
 
 /* Device buffers, asynchronous on `stream`; in, out and work 16-byte aligned; out_len, status
  * and bad_segment are DEVICE pointers. No allocation, no host synchronisation: every byte of
- * scratch comes from `work`. flags: HC_FLAG_DIFF | HC_FLAG_ADAPT. The return value reports
+ * scratch comes from `work`. flags: HC_FLAG_DIFF | HC_FLAG_ADAPT, and for the encoder
+ * HC_SEG_CHECK_CRC32 (work_bytes must then reach hc_seg_compress_work_bound2). The return value reports
  * argument / launch errors only (and HC_ERR_WIDTH / _MATRIX_SIZE / _DIMS, decided on the host).
  *
  * The encoder codes every segment into a slot of hc_compress_bound(segment) bytes inside `work`
  * and then gathers the slots into `out`: the slots are bound-sized, not guessed and retried, so
  * the work bound is about 6x the input (plus the adaptive batch workspace for -a). */
 uint64_t hc_seg_compress_work_bound(uint64_t in_len, uint64_t seg_bytes, int use_adapt, uint64_t width);
+uint64_t hc_seg_compress_work_bound2(uint64_t in_len, uint64_t seg_bytes, uint32_t flags, uint64_t width);
 int hc_seg_compress_dev(const uint8_t *in, uint64_t in_len, uint32_t flags, uint64_t width, uint64_t seg_bytes,
                         uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status,
                         void *work, uint64_t work_bytes, void *stream);
 /* The decoder needs the header on the host (hc_seg_info of the first 48 bytes) to size its
  * launches; the device bytes are checked against it. Segments decode in place into `out`. The
- * buffer behind `in` must be readable up to in_len rounded up to a multiple of 4. */
+ * buffer behind `in` must be readable up to in_len rounded up to a multiple of 4. Both kinds of
+ * container go through these two; info must equal the device header, the check kind included. */
 uint64_t hc_seg_decompress_work_bound(const hc_seg_info_t *info, uint64_t in_len);
 int hc_seg_decompress_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info,
                           uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status,
                           uint64_t *bad_segment, void *work, uint64_t work_bytes, void *stream);
+
+/* CRC-32 (zlib's crc32: reflected polynomial 0xEDB88320, init and final xor 0xFFFFFFFF) of
+ * n_ranges byte ranges, the kernel behind the checked container: crc[i] of in[in_offs[i] ..
+ * +lens[i]). DEVICE pointers, asynchronous on `stream`; any alignment, any length (0: crc 0), any
+ * n_ranges (0: nothing is done). No byte outside a range is read. */
+int hc_crc32_batch(const uint8_t *in, const uint64_t *in_offs, const uint64_t *lens, uint32_t n_ranges,
+                   uint32_t *crc, void *stream);
 
 /* Allocation caches. The single-buffer API keeps device scratch between calls (per device,
  * at most 1 GiB each) and the host-buffer batch API keeps its pipeline buffers (per device;

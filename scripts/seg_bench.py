@@ -8,6 +8,10 @@ call is a synchronous host-buffer call, timed with the host clock around it (cop
 on both sides), median of the repeats after warm-up. Prints one JSON line.
 
   scripts/seg_bench.py                       the sweep
+  scripts/seg_bench.py --check               adds the checked container (a CRC-32 per segment,
+                                             hc_seg_compress2 with HC_SEG_CHECK_CRC32) beside each
+                                             unchecked figure
+  scripts/seg_bench.py --no-whole --sizes 65536   the segmented calls alone, at the sizes named
   scripts/seg_bench.py --trace-run           a few segmented calls only, to be run under
                                              `rocprofv3 --kernel-trace --stats -- python ...`
   scripts/seg_bench.py --glue-from STATS.csv adds the glue kernels' share of device time, read
@@ -30,7 +34,8 @@ import hcodec as hc  # noqa: E402
 SIDE = 4096
 MODES = {"-m": (1, 0), "-a -m": (1, 1), "-a": (0, 1)}
 SIZES = (16384, 65536, 262144)
-GLUE = ("seg_plan_kernel", "seg_seal_kernel", "seg_gather_kernel", "seg_open_kernel", "seg_close_kernel")
+GLUE = ("seg_plan_kernel", "seg_seal_kernel", "seg_gather_kernel", "seg_open_kernel", "seg_close_kernel",
+        "crc32_kernel")
 
 
 def photo():
@@ -49,8 +54,8 @@ class Buffers:
         self.L = hc.lib()
         self.raw = raw
         self.src = ctypes.cast(ctypes.c_char_p(raw), ctypes.c_void_p)
-        self.cap = max(int(self.L.hc_seg_compress_bound(len(raw), 16384, 0, SIDE)),
-                       int(self.L.hc_seg_compress_bound(len(raw), 16384, 1, SIDE)),
+        self.cap = max(hc.seg_compress_bound(len(raw), 16384, False, SIDE, check=True),
+                       hc.seg_compress_bound(len(raw), 16384, True, SIDE, check=True),
                        hc.compress_bound(len(raw), True))
         self.enc = ctypes.create_string_buffer(self.cap)
         self.dec = ctypes.create_string_buffer(len(raw))
@@ -59,9 +64,14 @@ class Buffers:
     def p(self, b):
         return ctypes.cast(b, ctypes.c_void_p)
 
-    def seg_encode(self, diff, adapt, seg):
-        rc = self.L.hc_seg_compress(self.src, len(self.raw), diff, adapt, SIDE, seg, self.p(self.enc), self.cap,
-                                    ctypes.byref(self.n))
+    def seg_encode(self, diff, adapt, seg, check=False):
+        if check:
+            flags = (hc.HC_FLAG_DIFF if diff else 0) | (hc.HC_FLAG_ADAPT if adapt else 0) | hc.HC_SEG_CHECK_CRC32
+            rc = self.L.hc_seg_compress2(self.src, len(self.raw), flags, SIDE, seg, self.p(self.enc), self.cap,
+                                         ctypes.byref(self.n))
+        else:
+            rc = self.L.hc_seg_compress(self.src, len(self.raw), diff, adapt, SIDE, seg, self.p(self.enc), self.cap,
+                                        ctypes.byref(self.n))
         assert rc == 0, rc
         return self.n.value
 
@@ -117,6 +127,9 @@ def main():
     ap.add_argument("--glue-from")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--whole-reps", type=int, default=2)
+    ap.add_argument("--check", action="store_true")
+    ap.add_argument("--no-whole", action="store_true")
+    ap.add_argument("--sizes", type=int, nargs="+", default=list(SIZES))
     a = ap.parse_args()
     if not hc.device_ok():
         sys.exit("seg_bench.py needs a gfx950 device: " + hc.device_info())
@@ -124,28 +137,38 @@ def main():
     if a.trace_run:
         for diff, adapt in MODES.values():
             for _ in range(3):
-                b.seg_decode(b.seg_encode(diff, adapt, 65536))
+                b.seg_decode(b.seg_encode(diff, adapt, 65536, a.check))
             assert b.exact()
         return
     res = {"input": f"synthetic photo {SIDE}x{SIDE} ({len(b.raw)} bytes)", "timing":
            "host clock around each synchronous host-buffer call (copies included), median [min, max] ms",
            "modes": {}}
     for name, (diff, adapt) in MODES.items():
-        n = b.whole_encode(diff, adapt)
-        enc = timed(lambda: b.whole_encode(diff, adapt), 0, a.whole_reps)
-        dec = timed(lambda: b.whole_decode(n), 1, a.whole_reps)
-        assert b.exact()
-        m = {"whole": {"bytes": n, "encode_ms": enc, "decode_ms": dec}, "segmented": {}}
-        for seg in SIZES:
+        m = {"segmented": {}}
+        if not a.no_whole:
+            n = b.whole_encode(diff, adapt)
+            enc = timed(lambda: b.whole_encode(diff, adapt), 0, a.whole_reps)
+            dec = timed(lambda: b.whole_decode(n), 1, a.whole_reps)
+            assert b.exact()
+            m["whole"] = {"bytes": n, "encode_ms": enc, "decode_ms": dec}
+        for seg in a.sizes:
             k = b.seg_encode(diff, adapt, seg)
             e = timed(lambda: b.seg_encode(diff, adapt, seg), 2, a.reps)
             b.dec = ctypes.create_string_buffer(len(b.raw))
             d = timed(lambda: b.seg_decode(k), 2, a.reps)
             assert b.exact()
-            m["segmented"][str(seg)] = {
-                "bytes": k, "size_ratio": round(k / n, 5), "segments": hc.seg_count(len(b.raw), seg, adapt, SIDE),
-                "encode_ms": e, "decode_ms": d,
-                "encode_speedup": round(enc[0] / e[0], 1), "decode_speedup": round(dec[0] / d[0], 1)}
+            r = {"bytes": k, "segments": hc.seg_count(len(b.raw), seg, adapt, SIDE), "encode_ms": e, "decode_ms": d}
+            if not a.no_whole:
+                r.update({"size_ratio": round(k / n, 5), "encode_speedup": round(enc[0] / e[0], 1),
+                          "decode_speedup": round(dec[0] / d[0], 1)})
+            if a.check:
+                kc = b.seg_encode(diff, adapt, seg, True)
+                ec = timed(lambda: b.seg_encode(diff, adapt, seg, True), 2, a.reps)
+                b.dec = ctypes.create_string_buffer(len(b.raw))
+                dc = timed(lambda: b.seg_decode(kc), 2, a.reps)
+                assert b.exact()
+                r["check"] = {"bytes": kc, "encode_ms": ec, "decode_ms": dc}
+            m["segmented"][str(seg)] = r
         res["modes"][name] = m
     if a.glue_from:
         res["glue"] = glue_share(a.glue_from)
