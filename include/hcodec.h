@@ -178,7 +178,9 @@ int hc_decompress_host_batch(const uint8_t *const *in, const uint64_t *in_lens, 
 /* Device-side packing of many byte ranges into one buffer (e.g. a batch's encoded streams,
  * back to back, before they leave the GPU or cross to rank 0): copies lens[i] bytes from
  * in + in_offs[i] to out + out_offs[i] for every i. Asynchronous on `stream`; ranges must not
- * overlap. No reference counterpart (the reference writes one file per process). */
+ * overlap. Any byte alignment is accepted, of in, out and every offset, and no byte outside the
+ * destination ranges is written. No reference counterpart (the reference writes one file per
+ * process). */
 int hc_pack_batch(const uint8_t *in, const uint64_t *in_offs, const uint64_t *lens, uint32_t n_streams,
                   uint8_t *out, const uint64_t *out_offs, void *stream);
 
