@@ -194,6 +194,22 @@ constexpr uint32_t kRow = 16;       // u16 per cache entry
 #ifndef HC_ENC_BATCH
 #define HC_ENC_BATCH 1
 #endif
+// The symbol that ends a regular batch step is finished from what the step's lanes hold (model:
+// tests/fgk_handoff_model.py). HC_ENC_HANDOFF_MISS: an uncached symbol's byte and where[] word
+// come from the step's lanes instead of three more dependent LDS round trips.
+// HC_ENC_HANDOFF_LEVEL: a cached symbol with a reported level keeps the increments of its levels
+// below the report and walks from the reported level (no second test and store of every level).
+// Measured (C5 encode, alternating pairs): the miss hand-off alone 340.3 -> 330.2 ms, the level
+// hand-off alone 341.0 -> 338.3, both 332.8 / 332.8 / 334.0 against the miss hand-off alone 330.4 /
+// 332.1 / 331.5: four in ten reports on a photo stream are false, and each now costs a walk (exact
+// test, store, chase back, update_from) where update_fast ended it. Off.
+// scripts/build_rel.sh builds any combination (-DHC_ENC_HANDOFF_...=0 / 1).
+#ifndef HC_ENC_HANDOFF_MISS
+#define HC_ENC_HANDOFF_MISS 1
+#endif
+#ifndef HC_ENC_HANDOFF_LEVEL
+#define HC_ENC_HANDOFF_LEVEL 0
+#endif
 // decoder (narrow and wide layouts): HC_DEC_BATCH != 0: up to HC_DEC_PACK (4, 8, 12 or 16) codes
 // per step, packed by bit offset (one lane per code bit), from one read of the level tables at
 // every bit offset and one tentative commit (Dec::decode_batch; HC_DEC_BATCH 0: the one-symbol
@@ -358,6 +374,17 @@ __device__ __forceinline__ uint64_t groups9(uint32_t j)
     asm("s_mul_i32 %0, %1, 9" : "=s"(n) : "s"(j));
     asm("s_bfm_b64 %0, %1, 0" : "=s"(r) : "s"(n));
     return r;
+}
+// a regular encoder batch step that ends at lane fl (symbol jf = fl / 9): the lanes whose
+// increments are taken back -- from fl on, so that symbol jf's levels below a reported one stay
+// committed (HC_ENC_HANDOFF_LEVEL; a miss sits in its group's first lane), or from group jf on
+__device__ __forceinline__ uint64_t back_mask(uint32_t fl, uint32_t jf)
+{
+#if HC_ENC_HANDOFF_LEVEL
+    return ~0ull << fl;
+#else
+    return ~groups9(jf);
+#endif
 }
 // per lane: bit lane of m ? t : f (one v_cndmask on a scalar mask)
 __device__ __forceinline__ uint32_t sel(uint64_t m, uint32_t t, uint32_t f)
@@ -1491,9 +1518,9 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
     // bug detector) is checked once per chunk.
     const uint8_t *const sb = reinterpret_cast<const uint8_t *>(fgk.T.syms);
     uint8_t *const sb_w = reinterpret_cast<uint8_t *>(fgk.T.syms);
-    auto miss = [&](uint32_t sv) {
-        const uint32_t sym = uni(sv);
-        uint32_t s = uni(fgk.T.where[sym]) & 1023u;
+    // sym and its where[] word whw, both wave-uniform (a batch step hands over its own reads)
+    auto miss_at = [&](uint32_t sym, uint32_t whw) {
+        uint32_t s = whw & 1023u;
         const uint32_t fresh = s == 0;
         if (fresh) s = uni(fgk.split(sym));
         uint32_t pv;
@@ -1526,6 +1553,10 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
         } else {
             sink.push_bits(bits, d);
         }
+    };
+    auto miss = [&](uint32_t sv) {
+        const uint32_t sym = uni(sv);
+        miss_at(sym, uni(fgk.T.where[sym]));
     };
     // code symbols syms[0..ns) of the LDS buffer. The hot loop carries only vt, the records, the
     // cache's reference bits and its read pipeline: a miss or a failed leader test leaves it
@@ -1616,7 +1647,8 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
     //     where this takes 371);
     //  3. the first symbol with a failed level or without a cached path (the miss row's kMissPos)
     //     ends the batch: its increments and those after it are taken back, the code records of
-    //     the ones before it go to the sink, and it is coded alone (miss / update_path: walk).
+    //     the ones before it go to the sink, and it is coded alone (miss / update_path: walk),
+    //     its byte and where[] word taken from the step's lanes (`alone` below).
     //     Without such a symbol (the empty failure mask's ff1 is 0xFFFFFFFF) jf clamps to jmax;
     //     idle lane 63 holds the root, which never fails.
     // Per symbol ~10 instructions where the one-symbol loop takes ~26, and one dependent chain of
@@ -1654,6 +1686,48 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
         const uint32_t lkl = lane * kLv;
         constexpr uint64_t kL63 = 1ull << 63;
         uint32_t t = 0;
+        // The symbol syms[t] that ended a batch step (record lane sink.n), coded alone. stepd
+        // (wave-uniform): the step was a regular one, which hands over what its lanes hold: fl =
+        // the first lane of its failure mask, level fl - 9 jf of symbol jf; sv, wh its bytes and
+        // where[] words.
+        //  * Lane fl of sv and wh (every lane of group jf holds them) gives the symbol's byte and
+        //    where[] word, with them whether it is cached and which row is its own, instead of
+        //    three dependent reads of syms[t] and where[] (HC_ENC_HANDOFF_MISS).
+        //  * A cached symbol's levels below the report have kept their increments: they passed a
+        //    test that passes no level that fails. The walk starts at the reported level, where it
+        //    repeats the exact test (the report may be false); no level is tested or stored a
+        //    second time (HC_ENC_HANDOFF_LEVEL, off: see its definition). One read of the row gives the known path and the
+        //    record (the step's positions kept for them, one ds_bpermute and two ballots, cost the
+        //    small-alphabet kernel of the symbol source two VGPRs).
+        // Otherwise (a small-alphabet step, or a part compiled out) the symbol is looked up and
+        // every level tested again. One call site per kernel: the miss path stays inlined once.
+        auto alone = [&](bool stepd, uint32_t fl, uint32_t jf, uint32_t sv, uint32_t wh) __attribute__((always_inline)) {
+            const bool hm = HC_ENC_HANDOFF_MISS && stepd, hl = HC_ENC_HANDOFF_LEVEL && stepd;
+            uint32_t sym, whw;
+            if (hm) {
+                sym = lane_read(sv, fl);
+                whw = lane_read(wh, fl);
+            } else {
+                if (sink.n == 64) sink.pack();
+                sym = uni(sb[t]);
+                whw = uni(fgk.T.where[sym]);
+            }
+            const uint32_t ent = whw >> 10;
+            if (ent == 0) {
+                HC_PROF_BEGIN();
+                miss_at(sym, hm ? whw : uni(fgk.T.where[sym]));
+                HC_PROF_END(1);
+            } else {
+                HC_PROF_BEGIN();
+                uint32_t pv;
+                const uint32_t rc = fgk.pc_use(ent, fgk.pc_lane[ent * kRow], pv);
+                sink.push(rc);
+                // (update_path, with the reported level handed over)
+                const uint32_t k = hl ? fl - kLv * jf : fgk.update_fast(pv, [] {});
+                if (k != 0xFFFFFFFFu) fgk.walk(lane_read(pv, k), pv);
+                HC_PROF_END(2);
+            }
+        };
         // small-alphabet steps (above) while the stream has seen <= 16 symbols; re-checked only
         // after a symbol coded alone (splits happen there), so a regular step pays nothing for it
         if constexpr (!kSmall) {
@@ -1679,10 +1753,11 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
                 const uint32_t wn = *(const lds_u32 *)(size_t)wa;
                 // 2. the tests; 3. the increments from the first failing symbol on taken back
                 const uint64_t fm = (ballot(w1 < wn) & am) | ballot(pos == kMissPos);
-                jf = min(ff1(fm) / kLv, jmax);  // the failing lane's symbol
+                const uint32_t fl = ff1(fm);
+                jf = min(fl / kLv, jmax);  // the failing lane's symbol
                 if (jf < jmax) {
                     const uint32_t vdec = sel(kL63, (jf - jmax) * kIncU, 0u - kIncU);
-                    __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am & ~groups9(jf), wa, scb),
+                    __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am & back_mask(fl, jf), wa, scb),
                                            vdec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                 }
                 const uint32_t q = lane - sink.n;  // record lane q of the batch: symbol q's record
@@ -1696,23 +1771,9 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
                 __builtin_amdgcn_wave_barrier();
                 sink.n += jf;
                 t += jf;
-                if (jf < jmax) {  // symbol t: not cached, or a level reported (small: deeper than 4): alone
+                if (jf < jmax) {  // symbol t: not cached, or a level reported: alone
                     HC_CNT(2);
-                    if (sink.n == 64) sink.pack();
-                    const uint32_t sym = uni(sb[t]);
-                    const uint32_t ent = uni(fgk.T.where[sym]) >> 10;
-                    if (ent == 0) {
-                        HC_PROF_BEGIN();
-                        miss(sym);
-                        HC_PROF_END(1);
-                    } else {
-                        HC_PROF_BEGIN();
-                        uint32_t pv;
-                        const uint32_t rc = fgk.pc_use(ent, fgk.pc_lane[ent * kRow], pv);
-                        sink.push(rc);
-                        fgk.update_path(pv);
-                        HC_PROF_END(2);
-                    }
+                    alone(true, fl, jf, sv, wh);
                     ++t;
                 }
             }
@@ -1720,6 +1781,7 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
             bool small = fgk.nyt >= kSmallNyt;
             while (t < ns) {
                 uint32_t jf, jmax;
+                uint32_t fl = 0, sv = 0, wh = 0;  // of a regular step, for the symbol that ends it
                 if (small) {
                     // (the lane index opaque: these per-lane values are made here, not hoisted to the
                     // kernel's entry beside the regular step's)
@@ -1785,8 +1847,8 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
                         if (sink.n > 64 - kBatch) sink.pack();
                         HC_CNT(1);
                         jmax = min(kBatch, ns - t);
-                        const uint32_t sv = opaque(*(const lds_u8 *)(size_t)(svb + t));
-                        const uint32_t wh = opaque(*(const lds_u16 *)(size_t)(whb + 2 * sv));
+                        sv = opaque(*(const lds_u8 *)(size_t)(svb + t));
+                        wh = opaque(*(const lds_u16 *)(size_t)(whb + 2 * sv));
                         const uint32_t e = wh >> 10;
                         uint32_t pos = opaque(*(const lds_u16 *)(size_t)(rowb + 32 * e));
                         // lane 63 (idle) holds the root and adds one increment per batch symbol
@@ -1801,10 +1863,11 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
                         const uint32_t wn = *(const lds_u32 *)(size_t)wa;
                         // 2. the tests; 3. the increments from the first failing symbol on taken back
                         const uint64_t fm = (ballot(w1 < wn) & am) | ballot(pos == kMissPos);
-                        jf = min(ff1(fm) / kLv, jmax);  // the failing lane's symbol
+                        fl = ff1(fm);
+                        jf = min(fl / kLv, jmax);  // the failing lane's symbol
                         if (jf < jmax) {
                             const uint32_t vdec = sel(kL63, (jf - jmax) * kIncU, 0u - kIncU);
-                            __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am & ~groups9(jf), wa, scb),
+                            __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am & back_mask(fl, jf), wa, scb),
                                                    vdec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
                         }
                         const uint32_t q = lane - sink.n;  // record lane q of the batch: symbol q's record
@@ -1822,21 +1885,7 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
                 }
                 if (jf < jmax) {  // symbol t: not cached, or a level reported (small: deeper than 4): alone
                     HC_CNT(2);
-                    if (sink.n == 64) sink.pack();
-                    const uint32_t sym = uni(sb[t]);
-                    const uint32_t ent = uni(fgk.T.where[sym]) >> 10;
-                    if (ent == 0) {
-                        HC_PROF_BEGIN();
-                        miss(sym);
-                        HC_PROF_END(1);
-                    } else {
-                        HC_PROF_BEGIN();
-                        uint32_t pv;
-                        const uint32_t rc = fgk.pc_use(ent, fgk.pc_lane[ent * kRow], pv);
-                        sink.push(rc);
-                        fgk.update_path(pv);
-                        HC_PROF_END(2);
-                    }
+                    alone(!small, fl, jf, sv, wh);
                     ++t;
                     small = kSmall && fgk.nyt >= kSmallNyt;
                 }

@@ -7,10 +7,11 @@ cd "$(dirname "$0")/.."
 name=$1; shift
 out=abvar/$name
 mkdir -p "$out"
-make -s -C huffman-codec_amd build/hc_adapt.o build/hc_capi.o build/hc_synth.o build/hc_pipe.o
+make -s -C huffman-codec_amd build/hc_adapt.o build/hc_capi.o build/hc_synth.o build/hc_pipe.o build/hc_seg.o build/hc_crc.o
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Iinclude -Ihuffman-codec_amd/csrc -Wall -Wno-pass-failed \
     -mllvm -structurizecfg-skip-uniform-regions=1 "$@" -c huffman-codec_amd/csrc/hc_fgk.hip -o "$out/hc_fgk.o"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$out/libhcodec.so" "$out/hc_fgk.o" \
-    huffman-codec_amd/build/hc_adapt.o huffman-codec_amd/build/hc_capi.o huffman-codec_amd/build/hc_synth.o huffman-codec_amd/build/hc_pipe.o
+    huffman-codec_amd/build/hc_adapt.o huffman-codec_amd/build/hc_capi.o huffman-codec_amd/build/hc_synth.o huffman-codec_amd/build/hc_pipe.o \
+    huffman-codec_amd/build/hc_seg.o huffman-codec_amd/build/hc_crc.o
 rm -f "$out/hc_fgk.o"
 echo "built $out/libhcodec.so"

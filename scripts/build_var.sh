@@ -8,7 +8,7 @@ out=abvar/$name
 mkdir -p "$out/obj"
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Iinclude -Ihuffman-codec_amd/csrc -Wall -Wno-pass-failed -mllvm -structurizecfg-skip-uniform-regions=1 -DHC_DEBUG_HOOKS"
 pids=()
-for s in hc_fgk hc_adapt hc_capi hc_synth hc_pipe; do
+for s in hc_fgk hc_adapt hc_capi hc_synth hc_pipe hc_seg hc_crc; do
     /opt/rocm/bin/hipcc $FLAGS "$@" -c huffman-codec_amd/csrc/$s.hip -o "$out/obj/$s.o" &
     pids+=($!)
 done
