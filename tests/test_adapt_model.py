@@ -6,8 +6,10 @@ reproduces applyRLE byte for byte, and choosing + assembling reproduces applyAda
 (transform.cpp:294-328) — so the kernels built on these pieces are pinned before they run."""
 import random
 
+import numpy as np
 import pytest
 
+import adapt_big_cases as C
 import adapt_cost_model as M
 
 
@@ -105,6 +107,56 @@ def test_big_block_costs_from_tile_pieces(oracle_mod, kind):
             hc, vc = M.big_block_cost(hp, vp, W, H, B, i)
             assert hc == len(oracle_mod.rle(bytes(M.scan(D, W, x0, y0, sx, sy, True))))
             assert vc == len(oracle_mod.rle(bytes(M.scan(D, W, x0, y0, sx, sy, False))))
+
+
+def _check_big_blocks(oracle_mod, m2d, B, use_diff):
+    """every block of size B >= 256 of the matrix: big_block_cost from the tile pieces equals the
+    oracle's RLE length of both scans. Returns what the pieces exercised: the tiles a line of a
+    block spans at most, the shortest piece, and the outcomes of the first == prev_last
+    comparison that links a block's lines (h and v)."""
+    H, W = m2d.shape
+    m = m2d.reshape(-1).tolist()
+    D = np.array(M.diffed(m, use_diff), np.uint8).reshape(H, W)
+    hp, vp = M.tile_pieces(m, W, H, use_diff)
+    span, links = 0, set()
+    for i in range((-(-W // B)) * (-(-H // B))):
+        x0, y0, sx, sy = M.block_geo(W, H, B, i)
+        hc, vc = M.big_block_cost(hp, vp, W, H, B, i)
+        blk = D[y0:y0 + sy, x0:x0 + sx]
+        assert hc == len(oracle_mod.rle(np.ascontiguousarray(blk).reshape(-1))), (B, i, use_diff)
+        assert vc == len(oracle_mod.rle(np.ascontiguousarray(blk.T).reshape(-1))), (B, i, use_diff)
+        span = max(span, sx // M.TILE, sy // M.TILE)
+        links |= {("h", bool(blk[r, 0] == blk[r - 1, -1])) for r in range(1, sy)}
+        links |= {("v", bool(blk[0, c] == blk[-1, c - 1])) for c in range(1, sx)}
+    shortest = min(p[4] for p in list(hp.values()) + list(vp.values()))
+    return span, shortest, links
+
+
+_BOTH_LINKS = {("h", False), ("h", True), ("v", False), ("v", True)}
+
+
+@pytest.mark.parametrize("name", ["quilt-1025x513-q512", "longruns-1025x513-v"])
+def test_big_block_costs_from_tile_pieces_512(oracle_mod, name):
+    """B = 512 (and 256) on 1025 x 513, with and without the diff model: a block's line spans 4
+    full tiles, the last tile column and the last tile row give pieces of length 1, and the
+    link between a block's lines (first element against the previous line's last, prev_last)
+    is equal on some lines and unequal on others in both scans"""
+    m = C.pattern(name)
+    for use_diff in (False, True):
+        for B in (256, 512):
+            span, shortest, links = _check_big_blocks(oracle_mod, m, B, use_diff)
+            assert (span, shortest) == (B // M.TILE, 1)
+            assert use_diff or links == _BOTH_LINKS
+
+
+def test_big_block_costs_from_tile_pieces_1024(oracle_mod):
+    """B = 1024 on quilt(1032, 1025, 1024, 3): a line spans 8 full tiles, the tile row 1024 is
+    one element high and the edge blocks are 8 wide / 1 high"""
+    m = C.pattern("quilt-1032x1025-q1024")
+    for use_diff in (False, True):
+        span, shortest, links = _check_big_blocks(oracle_mod, m, 1024, use_diff)
+        assert (span, shortest) == (8, 1)
+        assert use_diff or links == _BOTH_LINKS
 
 
 def test_choose_and_assemble_is_apply_adapt(oracle_mod):
