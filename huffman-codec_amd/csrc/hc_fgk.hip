@@ -59,6 +59,10 @@ static uint32_t g_dec_small = 0;
 // HC_DEC_PACK)
 __device__ uint32_t g_dec_pack = 16;
 __device__ __forceinline__ uint32_t dec_pack_max(uint32_t k) { return min(k, (uint32_t)__builtin_amdgcn_readfirstlane(g_dec_pack)); }
+// the most symbols one regular encoder batch step takes (code_all_batch; hc_debug_set_enc_pack: 1,
+// 7 or HC_ENC_PACK)
+__device__ uint32_t g_enc_pack = 16;
+__device__ __forceinline__ uint32_t enc_pack_max(uint32_t k) { return min(k, (uint32_t)__builtin_amdgcn_readfirstlane(g_enc_pack)); }
 __device__ __forceinline__ uint64_t *trace_buf() { return g_trace; }
 __device__ __forceinline__ uint32_t window_bytes() { return __builtin_amdgcn_readfirstlane(g_window); }
 static uint32_t min_tree() { return g_min_tree; }
@@ -66,6 +70,7 @@ static uint32_t enc_tab() { return g_enc_tab; }
 static uint32_t dec_small() { return g_dec_small; }
 #else
 __device__ __forceinline__ uint32_t dec_pack_max(uint32_t k) { return k; }
+__device__ __forceinline__ uint32_t enc_pack_max(uint32_t k) { return k; }
 __device__ __forceinline__ uint64_t *trace_buf() { return nullptr; }
 __device__ __forceinline__ uint32_t window_bytes() { return 1u << 30; }
 static uint32_t min_tree() { return 0; }
@@ -186,14 +191,18 @@ constexpr uint32_t kInsertDepth = HC_INSERT_DEPTH;
 // encoder: a miss chases this many levels, then looks the position reached up in the path cache
 constexpr uint32_t kProbe = HC_PROBE;
 constexpr uint32_t kRow = 16;       // u16 per cache entry
-// 1: path-cache streams (narrow and wide layouts) code cached symbols seven at a time
-// (code_all_batch). Code records come from ballots of the positions' parities (C5 encode 433 ->
-// 412 ms against reading the cache rows' record words: two LDS operations fewer per step).
+// 1: path-cache streams (narrow and wide layouts) code cached symbols up to HC_ENC_PACK (1..16)
+// at a time, packed by path depth (code_all_batch). A symbol's depth and its code record both
+// come from one read of its cache row's record word.
 // Measured and dropped: uncached symbols joining the batch with lane-parallel chased paths,
 // inserted into the cache after the commit (570 ms)
 #ifndef HC_ENC_BATCH
 #define HC_ENC_BATCH 1
 #endif
+#ifndef HC_ENC_PACK
+#define HC_ENC_PACK 16
+#endif
+static_assert(HC_ENC_PACK >= 1 && HC_ENC_PACK <= 16, "a step's symbols are the lanes of one DPP row");
 // The symbol that ends a regular batch step is finished from what the step's lanes hold (model:
 // tests/fgk_handoff_model.py). HC_ENC_HANDOFF_MISS: an uncached symbol's byte and where[] word
 // come from the step's lanes instead of three more dependent LDS round trips.
@@ -365,27 +374,6 @@ __device__ __forceinline__ uint64_t below_mask(uint32_t k)
     asm("s_bfm_b64 %0, %1, 0" : "=s"(r) : "s"(k));
     return r;
 }
-// the lanes of the first j groups of nine, (1 << 9 j) - 1 for j <= 7, on the scalar unit (left to
-// itself the compiler may form 9 j on the VALU where SGPRs are scarce)
-__device__ __forceinline__ uint64_t groups9(uint32_t j)
-{
-    uint32_t n;
-    uint64_t r;
-    asm("s_mul_i32 %0, %1, 9" : "=s"(n) : "s"(j));
-    asm("s_bfm_b64 %0, %1, 0" : "=s"(r) : "s"(n));
-    return r;
-}
-// a regular encoder batch step that ends at lane fl (symbol jf = fl / 9): the lanes whose
-// increments are taken back -- from fl on, so that symbol jf's levels below a reported one stay
-// committed (HC_ENC_HANDOFF_LEVEL; a miss sits in its group's first lane), or from group jf on
-__device__ __forceinline__ uint64_t back_mask(uint32_t fl, uint32_t jf)
-{
-#if HC_ENC_HANDOFF_LEVEL
-    return ~0ull << fl;
-#else
-    return ~groups9(jf);
-#endif
-}
 // per lane: bit lane of m ? t : f (one v_cndmask on a scalar mask)
 __device__ __forceinline__ uint32_t sel(uint64_t m, uint32_t t, uint32_t f)
 {
@@ -512,7 +500,8 @@ struct Fgk {
                 for (uint32_t i = lane; i < 516; i += 64) T.pcode[i] = 0;
             } else {
                 for (uint32_t i = lane; i < kSlots * kRow; i += 64) T.pc[i] = (i % kRow) < kSlotDepth ? 0xFFFF : 0;
-                if (lane < kRow) T.pc_miss[lane] = lane == 0 ? kMissPos : kRoot;
+                // (word 12, the code record: 1 = depth 0, no lane of a packed batch step)
+                if (lane < kRow) T.pc_miss[lane] = lane == 0 ? kMissPos : (lane == kSlotDepth ? 1u : kRoot);
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -1634,28 +1623,37 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
     // tests/fgk_batch_model.py, test tests/test_batch_model.py).
     // Between swaps and splits the tree's shape is fixed and an update only adds 1 to the
     // weights on the symbol's root path, so the updates of consecutive cached symbols commute.
-    // Seven symbols at a time, lane 9 j + l taking level l of symbol j's cached path (level d =
-    // its depth: the root, counted once; l > d: root padding), the decoder's tentative commit
-    // (Dec::decode_batch):
-    //  1. every path position of every batch symbol gets its increment (one LDS add: +1024 to the
-    //     narrow weight word, +1 to a wide weight, the root once per symbol), the words of the
-    //     next positions having been read before;
+    // Up to HC_ENC_PACK (16) symbols at a time, packed by path depth as the decoder packs codes by
+    // bit offset (Dec::decode_batch; model: tests/fgk_encpack_model.py): symbol j's d_j path
+    // positions (levels 0 .. d_j - 1 of its cached row) take lanes S_j .. S_j + d_j - 1, S_j the
+    // depths of the symbols before it; no lane pads a short path, lane 63 is the root. The step:
+    //  0. lane j (of every row of 16 lanes) reads symbol t + j's byte, its where[] word and word
+    //     12 of its row, the finished code record 1 << d_j | code bits: the top bit's index is the
+    //     depth (the miss row's record is 1: depth 0; measured and dropped: the depths as sixteen
+    //     nibbles in scalar registers, kept beside pc_insert, which takes the record's read off the
+    //     step's chain of dependent LDS round trips: C5 encode 320.5 ms against 318.1), four row-DPP
+    //     adds give the starts, and the
+    //     step takes the symbols before the first of: the cap, the pass's end, a symbol without a
+    //     row, a symbol whose last lane would pass lane 62. A mark sent to every start lane
+    //     (ds_permute) and one ballot give each lane its symbol, one ds_bpermute of that symbol's
+    //     row address less its start the word to read: the lane's path position;
+    //  1. every path position of every symbol taken gets its increment (one LDS add: +1024 to the
+    //     narrow weight word, +1 to a wide weight, the root once per symbol by lane 63), the words
+    //     of the next positions having been read before;
     //  2. a level fails when that next word is below the position's word after the adds -- the
-    //     one-symbol loop's update_fast test with every batch symbol through the position counted
+    //     one-symbol loop's update_fast test with every step symbol through the position counted
     //     as earlier and none through the next one, so it reports levels falsely at worst (the
     //     exact counts, from membership bits ORed into the body words, measured 394 ms on C5
-    //     where this takes 371);
-    //  3. the first symbol with a failed level or without a cached path (the miss row's kMissPos)
-    //     ends the batch: its increments and those after it are taken back, the code records of
-    //     the ones before it go to the sink, and it is coded alone (miss / update_path: walk),
-    //     its byte and where[] word taken from the step's lanes (`alone` below).
-    //     Without such a symbol (the empty failure mask's ff1 is 0xFFFFFFFF) jf clamps to jmax;
-    //     idle lane 63 holds the root, which never fails.
-    // Per symbol ~10 instructions where the one-symbol loop takes ~26, and one dependent chain of
-    // LDS round trips per batch instead of per symbol.
-    // seven symbols in groups of nine lanes (levels 0..8: every cached path), the root's
-    // increments by lane 63 in the same adds (measured: six symbols in groups of ten, the root in
-    // each group, C5 encode 369 ms against 349)
+    //     where the tentative test took 371);
+    //  3. the first symbol with a failed level ends the step: its increments and those after it
+    //     are taken back; so does a symbol without a cached row, which never got lanes. Record
+    //     lane sink.n + q takes symbol q's record as lane q read it (one ds_bpermute), for the
+    //     symbols before that one, and it is coded alone (miss / update_path: walk), its byte and
+    //     where[] word taken from lane j of the step's reads (`alone` below).
+    // Measured against the layout before it, seven symbols in groups of nine lanes with root
+    // padding above each path (photo -c -m: six lanes in ten padding, 57 % of the steps ending at
+    // the cap of seven) and the records rebuilt from ballots of the positions' parities: DESIGN.md
+    // section 0, round 9.
     // Small alphabets (narrow layout, while at most 16 symbols are seen, so every position is >=
     // 480; model: tests/fgk_batch_model.py small_len, encode(small=True)). A run-heavy stream with a
     // few symbols (grad -c -m: 1, 3, 250, 255) ties on every row, and the tentative test below
@@ -1671,28 +1669,90 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
     // four) ends the step: the ones before it commit with one add, it is coded alone. grad:
     // 319 steps and 13 symbols alone per stream. Returns where the regular batches take over.
     constexpr uint32_t kSG = kSmallG, kSK = kSmallK;
-    constexpr uint32_t kBatch = 7, kLv = 9;  // (the masks: groups9)
-    static_assert(kBatch * kLv <= 63 && kLv >= kInsertDepth, "batch lanes: every cached path, lane 63 free");
+    constexpr uint32_t kPack = HC_ENC_PACK, kNone = 0xFFFFFFFFu;
+    static_assert(kInsertDepth <= 63 && kSlotDepth < kRow, "a cached path fits a step's lanes; word 12 is the record");
     constexpr uint32_t kIncU = kW ? 1u : 1024u;
     auto code_all_batch = [&](uint32_t ns) __attribute__((always_inline)) {
-        const uint32_t bj = lane < kBatch * kLv ? lane / kLv : 7u;  // the lane's symbol (7: idle)
-        const uint32_t bl = lane < kBatch * kLv ? lane % kLv : 0u;  // ... and level
-        const uint64_t idle = ~0ull << (kBatch * kLv);
-        const uint32_t rowb = lds_off16(&fgk.T.pc[0]) + 2 * bl - 2 * kRow;  // + 32 e: row e - 1 (e = 0: pc_miss)
+        const uint32_t pcb = lds_off16(&fgk.T.pc[0]) - 2 * kRow;  // + 32 e: row e - 1 (e = 0: pc_miss)
         const uint32_t wtb = lds_off(&fgk.T.wt[0]);
         const uint32_t whb = lds_off16(&fgk.T.where[0]);
         const uint32_t scb = lds_off(fgk.scr32());
-        const uint32_t svb = (uint32_t)(size_t)(const lds_u8 *)sb + bj;
-        const uint32_t lkl = lane * kLv;
         constexpr uint64_t kL63 = 1ull << 63;
         uint32_t t = 0;
+        // One regular step from symbol t on (the comment above). Returns the index in the step of
+        // the symbol that ended it and is to be coded alone (kNone: the cap, the lanes or the pass
+        // ended it), with t and sink.n moved past the symbols before it; sv, wh: lane j holds the
+        // byte and the where[] word of symbol j; lv: the level reported (HC_ENC_HANDOFF_LEVEL).
+        auto step = [&](uint32_t &sv, uint32_t &wh, uint32_t &lv) __attribute__((always_inline)) -> uint32_t {
+            if (sink.n > 64 - kPack) sink.pack();
+            HC_CNT(1);
+            const uint32_t lim = enc_pack_max(min(kPack, ns - t));  // 1..16
+            // 0. lane j of every row: symbol t + j (bytes past ns are older symbols of the buffer
+            // or the tree's words behind it: any byte names a where[] word)
+            const uint32_t ln = vreg(lane);  // (opaque: the lane's constants are made here, not kept from the kernel's entry)
+            sv = opaque(*(const lds_u8 *)(size_t)((uint32_t)(size_t)(const lds_u8 *)sb + t + (ln & 15u)));
+            wh = opaque(*(const lds_u16 *)(size_t)(whb + 2 * sv));
+            const uint32_t ra = pcb + ((wh >> 10) << 5);
+            const uint32_t rec = opaque(*(const lds_u16 *)(size_t)(ra + 2 * kSlotDepth));
+            const uint32_t d = 31u - (uint32_t)__builtin_clz(rec);  // (a row in use holds a record >= 2, the miss row 1)
+            uint32_t inc = d;  // the depths up to and with symbol j's
+            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xF, 0xF, true);
+            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xF, 0xF, true);
+            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xF, 0xF, true);
+            inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xF, 0xF, true);
+            // the symbols without a row, within the cap and the pass; the first symbol not taken
+            const uint32_t mm = (uint32_t)ballot(wh < 1024u) & ((1u << lim) - 1u);
+            const uint32_t jmax = (uint32_t)__builtin_ctz(mm | (uint32_t)ballot(inc > 63u) | (1u << lim));
+            lv = 0;
+            if (jmax == 0) return 0;  // (a cached path is at most kInsertDepth lanes: the first symbol has no row)
+            const uint32_t se = lane_read(inc, jmax - 1);  // the lanes of the symbols taken, <= 63
+            const uint32_t exc = inc - d;                  // symbol j's first lane
+            // lane j < jmax sends a mark to symbol j's first lane (the other lanes to lane 63, whose
+            // bit is not used); the lane's symbol: the starts in lanes 1..lane
+            const uint32_t to = sel(below_mask(jmax), exc << 2, 63u << 2);
+            const uint64_t sm = ballot(__builtin_amdgcn_ds_permute((int)to, 1) != 0);
+            const uint32_t jv = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 33), __builtin_amdgcn_mbcnt_lo((uint32_t)(sm >> 1), 0u));
+            // the lane's level l = lane - S_j of its symbol's row: the word at row + 2 l
+            const uint32_t rl = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(jv << 2), (int)(ra - 2 * exc));
+            const uint64_t act = below_mask(se);  // the lanes of the symbols taken
+            uint32_t pos = opaque(*(const lds_u16 *)(size_t)(rl + 2 * ln));
+            pos = sel(act, pos, kRoot);  // lane 63 and the idle lanes hold the root; lane 63 adds one increment per symbol
+            const uint32_t wa = wtb + 4 * pos;
+            // 1. tentative increments (each path position once, the root once per symbol)
+            const uint32_t w1 = *(const lds_u32 *)(size_t)(wa + 4);
+            __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(act | kL63, wa, scb), sel(kL63, jmax * kIncU, kIncU),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            const uint32_t wn = *(const lds_u32 *)(size_t)wa;
+            // 2. the tests; 3. the increments from the first failing symbol on taken back
+            const uint64_t fm = ballot(w1 < wn) & act;
+            uint32_t jf = jmax;
+            if (fm) {
+                const uint32_t fl = ff1(fm);
+                jf = lane_read(jv, fl);  // the failing lane's symbol
+                const uint32_t sj = lane_read(exc, jf);
+                lv = fl - sj;
+                // (HC_ENC_HANDOFF_LEVEL: symbol jf's levels below the reported one stay committed)
+                const uint64_t back = (act & (~0ull << (HC_ENC_HANDOFF_LEVEL ? fl : sj))) | kL63;
+                __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(back, wa, scb), sel(kL63, (jf - jmax) * kIncU, 0u - kIncU),
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            }
+            // record lane sink.n + q takes symbol q's record, which lane q read
+            const uint32_t q = ln - sink.n;
+            const uint32_t r = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q << 2), (int)rec);
+            sink.vrec = q < jf ? r : sink.vrec;
+            __builtin_amdgcn_wave_barrier();
+            sink.n += jf;
+            t += jf;
+            // symbol jf: a level reported, or (none reported: jf = jmax) not cached
+            return fm || ((mm >> jf) & 1u) ? jf : kNone;
+        };
         // The symbol syms[t] that ended a batch step (record lane sink.n), coded alone. stepd
-        // (wave-uniform): the step was a regular one, which hands over what its lanes hold: fl =
-        // the first lane of its failure mask, level fl - 9 jf of symbol jf; sv, wh its bytes and
-        // where[] words.
-        //  * Lane fl of sv and wh (every lane of group jf holds them) gives the symbol's byte and
-        //    where[] word, with them whether it is cached and which row is its own, instead of
-        //    three dependent reads of syms[t] and where[] (HC_ENC_HANDOFF_MISS).
+        // (wave-uniform): the step was a regular one, which hands over what its lanes hold: ja =
+        // the symbol's index in the step, lv its reported level (if one was); sv, wh the step's
+        // bytes and where[] words.
+        //  * Lane ja of sv and wh gives the symbol's byte and where[] word, with them whether it is
+        //    cached and which row is its own, instead of three dependent reads of syms[t] and
+        //    where[] (HC_ENC_HANDOFF_MISS).
         //  * A cached symbol's levels below the report have kept their increments: they passed a
         //    test that passes no level that fails. The walk starts at the reported level, where it
         //    repeats the exact test (the report may be false); no level is tested or stored a
@@ -1701,12 +1761,12 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
         //    small-alphabet kernel of the symbol source two VGPRs).
         // Otherwise (a small-alphabet step, or a part compiled out) the symbol is looked up and
         // every level tested again. One call site per kernel: the miss path stays inlined once.
-        auto alone = [&](bool stepd, uint32_t fl, uint32_t jf, uint32_t sv, uint32_t wh) __attribute__((always_inline)) {
+        auto alone = [&](bool stepd, uint32_t ja, uint32_t lv, uint32_t sv, uint32_t wh) __attribute__((always_inline)) {
             const bool hm = HC_ENC_HANDOFF_MISS && stepd, hl = HC_ENC_HANDOFF_LEVEL && stepd;
             uint32_t sym, whw;
             if (hm) {
-                sym = lane_read(sv, fl);
-                whw = lane_read(wh, fl);
+                sym = lane_read(sv, ja);
+                whw = lane_read(wh, ja);
             } else {
                 if (sink.n == 64) sink.pack();
                 sym = uni(sb[t]);
@@ -1723,7 +1783,7 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
                 const uint32_t rc = fgk.pc_use(ent, fgk.pc_lane[ent * kRow], pv);
                 sink.push(rc);
                 // (update_path, with the reported level handed over)
-                const uint32_t k = hl ? fl - kLv * jf : fgk.update_fast(pv, [] {});
+                const uint32_t k = hl ? lv : fgk.update_fast(pv, [] {});
                 if (k != 0xFFFFFFFFu) fgk.walk(lane_read(pv, k), pv);
                 HC_PROF_END(2);
             }
@@ -1733,56 +1793,21 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
         if constexpr (!kSmall) {
             // (the path-cache kernel: one regular batch step per pass of this loop)
             while (t < ns) {
-                uint32_t jf, jmax;
-                if (sink.n > 64 - kBatch) sink.pack();
-                HC_CNT(1);
-                jmax = min(kBatch, ns - t);
-                const uint32_t sv = opaque(*(const lds_u8 *)(size_t)(svb + t));
-                const uint32_t wh = opaque(*(const lds_u16 *)(size_t)(whb + 2 * sv));
-                const uint32_t e = wh >> 10;
-                uint32_t pos = opaque(*(const lds_u16 *)(size_t)(rowb + 32 * e));
-                // lane 63 (idle) holds the root and adds one increment per batch symbol
-                pos = sel(idle, kRoot, pos);
-                const uint32_t wa = wtb + 4 * pos;
-                const uint64_t am = (ballot(pos < kRoot) & groups9(jmax)) | (jmax ? kL63 : 0);
-                const uint32_t vinc = sel(kL63, jmax * kIncU, kIncU);
-                // 1. tentative increments (each path position once, the root once per symbol)
-                const uint32_t w1 = *(const lds_u32 *)(size_t)(wa + 4);
-                __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am, wa, scb), vinc, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_WAVEFRONT);
-                const uint32_t wn = *(const lds_u32 *)(size_t)wa;
-                // 2. the tests; 3. the increments from the first failing symbol on taken back
-                const uint64_t fm = (ballot(w1 < wn) & am) | ballot(pos == kMissPos);
-                const uint32_t fl = ff1(fm);
-                jf = min(fl / kLv, jmax);  // the failing lane's symbol
-                if (jf < jmax) {
-                    const uint32_t vdec = sel(kL63, (jf - jmax) * kIncU, 0u - kIncU);
-                    __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am & back_mask(fl, jf), wa, scb),
-                                           vdec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                }
-                const uint32_t q = lane - sink.n;  // record lane q of the batch: symbol q's record
-                // the code record 1 << d | bits (bit k: level k's parity, left = even) from two
-                // ballots: the group's parity bits below its first root lane
-                const uint64_t par = ballot(pos & 1u), rtm = ballot(pos == kRoot);
-                const uint32_t gb = lkl - sink.n * kLv;  // q * kLv
-                const uint32_t d = (uint32_t)__builtin_ctz((uint32_t)(rtm >> gb) | (1u << kLv));
-                const uint32_t r = __builtin_amdgcn_ubfe((uint32_t)(par >> gb), 0, d) | (1u << d);
-                sink.vrec = q < jf ? r : sink.vrec;
-                __builtin_amdgcn_wave_barrier();
-                sink.n += jf;
-                t += jf;
-                if (jf < jmax) {  // symbol t: not cached, or a level reported: alone
+                uint32_t sv, wh, lv;
+                const uint32_t ja = step(sv, wh, lv);
+                if (ja != kNone) {  // symbol t: not cached, or a level reported: alone
                     HC_CNT(2);
-                    alone(true, fl, jf, sv, wh);
+                    alone(true, ja, lv, sv, wh);
                     ++t;
                 }
             }
         } else {
             bool small = fgk.nyt >= kSmallNyt;
             while (t < ns) {
-                uint32_t jf, jmax;
-                uint32_t fl = 0, sv = 0, wh = 0;  // of a regular step, for the symbol that ends it
+                uint32_t ja = kNone;
+                uint32_t lv = 0, sv = 0, wh = 0;  // of a regular step, for the symbol that ends it
                 if (small) {
+                    uint32_t jf, jmax;
                     // (the lane index opaque: these per-lane values are made here, not hoisted to the
                     // kernel's entry beside the regular step's)
                     const uint32_t ln = vreg(lane);
@@ -1842,50 +1867,14 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
                         sink.n += jf;
                         t += jf;
                     } while (jf == jmax && t < ns);
+                    if (jf < jmax) ja = 0;  // (the symbol is looked up again)
                 } else {
-                    do {
-                        if (sink.n > 64 - kBatch) sink.pack();
-                        HC_CNT(1);
-                        jmax = min(kBatch, ns - t);
-                        sv = opaque(*(const lds_u8 *)(size_t)(svb + t));
-                        wh = opaque(*(const lds_u16 *)(size_t)(whb + 2 * sv));
-                        const uint32_t e = wh >> 10;
-                        uint32_t pos = opaque(*(const lds_u16 *)(size_t)(rowb + 32 * e));
-                        // lane 63 (idle) holds the root and adds one increment per batch symbol
-                        pos = sel(idle, kRoot, pos);
-                        const uint32_t wa = wtb + 4 * pos;
-                        const uint64_t am = (ballot(pos < kRoot) & groups9(jmax)) | (jmax ? kL63 : 0);
-                        const uint32_t vinc = sel(kL63, jmax * kIncU, kIncU);
-                        // 1. tentative increments (each path position once, the root once per symbol)
-                        const uint32_t w1 = *(const lds_u32 *)(size_t)(wa + 4);
-                        __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am, wa, scb), vinc, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        const uint32_t wn = *(const lds_u32 *)(size_t)wa;
-                        // 2. the tests; 3. the increments from the first failing symbol on taken back
-                        const uint64_t fm = (ballot(w1 < wn) & am) | ballot(pos == kMissPos);
-                        fl = ff1(fm);
-                        jf = min(fl / kLv, jmax);  // the failing lane's symbol
-                        if (jf < jmax) {
-                            const uint32_t vdec = sel(kL63, (jf - jmax) * kIncU, 0u - kIncU);
-                            __hip_atomic_fetch_add((uint32_t *)(lds_u32 *)(size_t)sel(am & back_mask(fl, jf), wa, scb),
-                                                   vdec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-                        }
-                        const uint32_t q = lane - sink.n;  // record lane q of the batch: symbol q's record
-                        // the code record 1 << d | bits (bit k: level k's parity, left = even) from two
-                        // ballots: the group's parity bits below its first root lane
-                        const uint64_t par = ballot(pos & 1u), rtm = ballot(pos == kRoot);
-                        const uint32_t gb = lkl - sink.n * kLv;  // q * kLv
-                        const uint32_t d = (uint32_t)__builtin_ctz((uint32_t)(rtm >> gb) | (1u << kLv));
-                        const uint32_t r = __builtin_amdgcn_ubfe((uint32_t)(par >> gb), 0, d) | (1u << d);
-                        sink.vrec = q < jf ? r : sink.vrec;
-                        __builtin_amdgcn_wave_barrier();
-                        sink.n += jf;
-                        t += jf;
-                    } while (jf == jmax && t < ns);
+                    do ja = step(sv, wh, lv);
+                    while (ja == kNone && t < ns);
                 }
-                if (jf < jmax) {  // symbol t: not cached, or a level reported (small: deeper than 4): alone
+                if (ja != kNone) {  // symbol t: not cached, or a level reported (small: deeper than 4): alone
                     HC_CNT(2);
-                    alone(!small, fl, jf, sv, wh);
+                    alone(!small, ja, lv, sv, wh);
                     ++t;
                     small = kSmall && fgk.nyt >= kSmallNyt;
                 }
@@ -3106,6 +3095,15 @@ extern "C" int hc_debug_set_dec_pack(uint32_t max)
     // for the build's HC_DEC_PACK
     uint32_t k = max == 1 || max == 7 ? max : 16u;
     return hipMemcpyToSymbol(HIP_SYMBOL(hc::g_dec_pack), &k, sizeof(k)) == hipSuccess ? 0 : HC_ERR_DEVICE;
+}
+
+extern "C" int hc_debug_set_enc_pack(uint32_t max)
+{
+    // the most symbols a regular encoder batch step takes in every later FGK launch on the current
+    // device (a device variable, like hc_debug_set_dec_pack's): 1, 7, or anything else for the
+    // build's HC_ENC_PACK
+    uint32_t k = max == 1 || max == 7 ? max : 16u;
+    return hipMemcpyToSymbol(HIP_SYMBOL(hc::g_enc_pack), &k, sizeof(k)) == hipSuccess ? 0 : HC_ERR_DEVICE;
 }
 
 extern "C" int hc_debug_set_enc_tab(uint32_t mode)

@@ -584,6 +584,17 @@ def debug_set_dec_pack(max_codes):
         raise HCodecError(f"hc_debug_set_dec_pack failed: {rc}")
 
 
+def debug_set_enc_pack(max_symbols):
+    """Test hook (debug build only, use_debug_build): the most symbols one regular batch step of the
+    FGK encoder takes (code_all_batch): 1, 7, or 16 (the build's own cap; any other value). A device
+    variable, like debug_set_dec_pack's: it holds for later launches on the current device only."""
+    f = _dbg().hc_debug_set_enc_pack
+    f.argtypes = [ctypes.c_uint32]
+    rc = f(int(max_symbols))
+    if rc:
+        raise HCodecError(f"hc_debug_set_enc_pack failed: {rc}")
+
+
 def debug_enc_votes(inp, in_offs, in_lens, use_diff, low_occ, status, stream=None):
     """Test hook (debug build only, use_debug_build): the encoder's per-stream mode vote alone
     (enc_mode_kernel) into status: -0x7A1 the path cache, -0x7A0 the level tables. low_occ: the

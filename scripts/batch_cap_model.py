@@ -17,6 +17,12 @@ step, symbols coded alone.
 
     python scripts/batch_cap_model.py --policy pack
     python scripts/batch_cap_model.py --policy hyst
+
+--policy encpack: the encoder's step packed by path depth (tests/fgk_encpack_model.py: up to 16 or
+12 cached symbols a step, one lane per path position while the depths sum to at most 63) against
+the 7 x 9 steps on streams 0..3.
+
+    python scripts/batch_cap_model.py --policy encpack
 """
 import argparse
 import os
@@ -100,6 +106,16 @@ def realisable(policy, n_sym):
                 line(f"decoder packed, <= {cap} codes", n, s1["steps"], s1["alone"], s0["steps"])
             t1, s1 = P.decode_packed(syms, cap=16, window=False, exit8=False)
             line("decoder packed, <= 16 codes, no window limit", n, s1["steps"], s1["alone"], s0["steps"])
+        elif policy == "encpack":
+            import fgk_encpack_model as E
+            c0, t0, s0 = P.encode_hyst(syms, 1)
+            line("encoder 7 x 9", n, s0["steps"], s0["alone"])
+            for cap in (16, 12):
+                c1, t1, s1 = E.encode_packed(syms, cap=cap)
+                assert c1 == c0 and t1.w == t0.w
+                line(f"encoder packed by depth, <= {cap} symbols", n, s1["steps",], s1["alone",], s0["steps"])
+                print(f"    {s1['empty',]} steps that took nothing (their first symbol had no row), "
+                      f"{s1['full',]} at the cap, {s1['end63',]} with all 63 lanes")
         else:
             c0, t0, s0 = P.encode_hyst(syms, 1)
             line("encoder 7 x 9", n, s0["steps"], s0["alone"])
@@ -113,7 +129,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stream", type=int, default=0)
     ap.add_argument("--symbols", type=int, default=60000)
-    ap.add_argument("--policy", choices=("oracle", "pack", "hyst"), default="oracle")
+    ap.add_argument("--policy", choices=("oracle", "pack", "hyst", "encpack"), default="oracle")
     a = ap.parse_args()
     if a.policy != "oracle":
         return realisable(a.policy, a.symbols)

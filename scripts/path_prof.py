@@ -6,7 +6,8 @@ g_trace[8 * stream + i] (lane 0 = the wave's whole life). s_memtime itself costs
 the shares are indicative, not exact.
 
     make -C huffman-codec_amd lib/libhcodec.so EXTRA=-DHC_PROF -B && cp ... abvar/P/
-    HC_LIB_PATH=abvar/P/libhcodec.so python scripts/path_prof.py [--streams 8192]
+    HC_LIB_PATH=abvar/P/libhcodec.so HC_DBG_LIB_PATH=abvar/P/libhcodec.so python scripts/path_prof.py [--streams 8192]
+(the script loads the debug library for hc_debug_set_trace: both paths name the HC_PROF build)
 """
 import argparse
 import ctypes
