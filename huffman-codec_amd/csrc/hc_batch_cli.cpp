@@ -3,7 +3,7 @@
 // process, main.cpp:202-220). Each output is byte-identical to what `huffman-codec` (and the
 // reference) writes for that file alone.
 //
-//   huffman-codec-batch [-c | -d] [-m] [-a [-w WIDTH]] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...
+//   huffman-codec-batch [-c | -d [-r OFFSET:LENGTH]] [-m] [-a [-w WIDTH]] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...
 //
 // Compression writes FILE.huf, decompression FILE without its .huf suffix (else FILE.out);
 // with -o into OUTDIR under the same base name. Files are read and written by a pool of
@@ -17,6 +17,11 @@
 // CRC-32 per segment. -d tells containers from plain streams by their first 8 bytes and sends them
 // through hc_seg_decompress_alloc, which verifies the checksums of a container that has them; a
 // failing segment reports "FILE: segment K: <message>".
+//
+// -r OFFSET:LENGTH with -d writes raw bytes [OFFSET, OFFSET + LENGTH) alone, under the same output
+// name, through hc_seg_decompress_range: only the segments that hold the range are uploaded and
+// decoded. Every FILE must then be a container; another one reports "FILE: -r needs a segmented
+// container" and counts as HC_ERR_UNSUPPORTED (65). A range outside a container is HC_ERR_ARG (71).
 #include <unistd.h>
 
 #include <algorithm>
@@ -39,7 +44,7 @@ const char *const kHelp =
     "USAGE:\n"
     "  huffman-codec-batch [-cm] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch [-cm] -a [-w WIDTH] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
-    "  huffman-codec-batch -d [-o OUTDIR] [-j THREADS] FILE... | -h\n"
+    "  huffman-codec-batch -d [-r OFFSET:LENGTH] [-o OUTDIR] [-j THREADS] FILE... | -h\n"
     "\n"
     "OPTION:\n"
     "  -c/-d  perform compression/decompression\n"
@@ -48,6 +53,8 @@ const char *const kHelp =
     "  -w     width of 2D data (default: 512)\n"
     "  -s     write segmented containers of BYTES-byte segments (0: 65536)\n"
     "  -k     with -s: store a CRC-32 of every segment, verified by -d\n"
+    "  -r     with -d: write only raw bytes [OFFSET, OFFSET + LENGTH) of every FILE,\n"
+    "         each a segmented container\n"
     "  -o     output directory (default: next to each input)\n"
     "  -j     file I/O threads (default: 8)\n"
     "  -h     show this help\n"
@@ -69,6 +76,30 @@ std::string out_path(const std::string &in, bool compress, const std::string &di
 }
 
 // run f(i) for i in [0, n) on `threads` host threads
+// "OFFSET:LENGTH", both decimal and nothing else
+bool parse_range(const char *arg, uint64_t &offset, uint64_t &length)
+{
+    uint64_t v[2] = {0, 0};
+    int k = 0;
+    bool digits = false;
+    for (const char *p = arg; *p; ++p) {
+        if (*p == ':' && k == 0 && digits) {
+            k = 1;
+            digits = false;
+            continue;
+        }
+        if (*p < '0' || *p > '9') return false;
+        const uint64_t d = (uint64_t)(*p - '0');
+        if (v[k] > (UINT64_MAX - d) / 10) return false;
+        v[k] = v[k] * 10 + d;
+        digits = true;
+    }
+    if (k != 1 || !digits) return false;
+    offset = v[0];
+    length = v[1];
+    return true;
+}
+
 template <class F>
 void parallel(size_t n, unsigned threads, F &&f)
 {
@@ -85,13 +116,13 @@ void parallel(size_t n, unsigned threads, F &&f)
 
 int main(int argc, char *argv[])
 {
-    bool compress = true, use_diff = false, use_adapt = false, segmented = false, check = false;
-    uint64_t seg_bytes = 0;
+    bool compress = true, use_diff = false, use_adapt = false, segmented = false, check = false, ranged = false;
+    uint64_t seg_bytes = 0, r_offset = 0, r_length = 0;
     std::string dir;
     uint64_t width = 512;
     unsigned threads = 8;
     int opt;
-    while ((opt = getopt(argc, argv, ":cdmaw:s:ko:j:h")) != -1) {
+    while ((opt = getopt(argc, argv, ":cdmaw:s:kr:o:j:h")) != -1) {
         switch (opt) {
         case 'c': compress = true; break;
         case 'd': compress = false; break;
@@ -103,6 +134,13 @@ int main(int argc, char *argv[])
             seg_bytes = std::stoull(optarg);
             break;
         case 'k': check = true; break;
+        case 'r':
+            ranged = true;
+            if (!parse_range(optarg, r_offset, r_length)) {
+                std::cerr << "ERROR: unrecognized option used\n";
+                return 2;
+            }
+            break;
         case 'o': dir = optarg; break;
         case 'j': threads = (unsigned)std::stoul(optarg); break;
         case 'h': std::cout << kHelp; return 0;
@@ -111,6 +149,10 @@ int main(int argc, char *argv[])
         }
     }
     if (check && !(compress && segmented)) {  // a checksum has nowhere to go but a container's index
+        std::cerr << "ERROR: unrecognized option used\n";
+        return 2;
+    }
+    if (ranged && compress) {  // a range is read, never written
         std::cerr << "ERROR: unrecognized option used\n";
         return 2;
     }
@@ -180,7 +222,16 @@ int main(int argc, char *argv[])
         for (size_t i = 0; i < n; ++i) {
             if (status[i]) continue;
             if (in[i].size() < 8 || !std::equal(kSegMagic, kSegMagic + 8, in[i].begin())) {
-                batch.push_back(i);
+                if (ranged) status[i] = -1;  // reported below as HC_ERR_UNSUPPORTED
+                else batch.push_back(i);
+                continue;
+            }
+            if (ranged) {
+                out[i].resize(std::min<uint64_t>(r_length, 520 * (uint64_t)in[i].size()));  // (no container decodes to more)
+                uint64_t len = 0;
+                status[i] = hc_seg_decompress_range(in[i].data(), in[i].size(), r_offset, r_length, out[i].data(),
+                                                    out[i].size(), &len, &bad_seg[i]);
+                out[i].resize(status[i] ? 0 : len);
                 continue;
             }
             uint8_t *p = nullptr;  // a segmented container
@@ -229,6 +280,11 @@ int main(int argc, char *argv[])
     parallel(n, threads, [&](size_t i) {
         if (status[i] == 5) {
             msgs[i] = files[i] + ": ERROR: given input file does not exist\n";
+            return;
+        }
+        if (status[i] == -1) {
+            status[i] = HC_ERR_UNSUPPORTED;
+            msgs[i] = files[i] + ": -r needs a segmented container\n";
             return;
         }
         if (status[i]) {

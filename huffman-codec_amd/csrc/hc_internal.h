@@ -65,6 +65,12 @@ struct CrcGate {
 hipError_t launch_crc32(const uint8_t *in, const uint64_t *offs, const uint64_t *lens, uint64_t n, uint32_t *crc,
                         const CrcGate &gate, hipStream_t st);
 
+// lens[i] bytes from src + soffs[i] to dst + doffs[i] for n ranges (hc_pipe.hip's pack_kernel, the
+// kernel behind hc_pack_batch), asynchronous on st: any byte alignment, no byte outside a source
+// range read, none outside a destination range written; an empty range costs nothing
+hipError_t launch_pack(const uint8_t *src, const uint64_t *soffs, const uint64_t *lens, uint32_t n, uint8_t *dst,
+                       const uint64_t *doffs, hipStream_t st);
+
 // frees the host-batch pipeline slots' cached buffers (hc_release_cached; slots in use by a
 // running call are left alone)
 void pipe_release();

@@ -440,6 +440,14 @@ void pipe_release()
         }
     }
 }
+
+hipError_t launch_pack(const uint8_t *src, const uint64_t *soffs, const uint64_t *lens, uint32_t n, uint8_t *dst,
+                       const uint64_t *doffs, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    pack_kernel<<<n < 65535 ? n : 65535, 256, 0, st>>>(src, soffs, lens, n, dst, doffs);
+    return hipGetLastError();
+}
 }  // namespace hc
 
 extern "C" {
@@ -467,9 +475,9 @@ int hc_pack_batch(const uint8_t *in, const uint64_t *in_offs, const uint64_t *le
 {
     if (n_streams == 0) return HC_OK;
     if (!in || !in_offs || !lens || !out || !out_offs) return HC_ERR_ARG;
-    pack_kernel<<<n_streams < 65535 ? n_streams : 65535, 256, 0, static_cast<hipStream_t>(stream)>>>(
-        in, in_offs, lens, n_streams, out, out_offs);
-    return hipGetLastError() == hipSuccess ? HC_OK : HC_ERR_DEVICE;
+    return hc::launch_pack(in, in_offs, lens, n_streams, out, out_offs, static_cast<hipStream_t>(stream)) == hipSuccess
+               ? HC_OK
+               : HC_ERR_DEVICE;
 }
 
 int hc_decompress_host_batch(const uint8_t *const *in, const uint64_t *in_lens, uint32_t n_streams,

@@ -1,0 +1,144 @@
+// hc_seg_index.h — the host's reading of a segmented container's header and index (HCSEG1,
+// include/hcodec.h): the cut rule, every header rule, the segments a byte range covers, and the
+// index scan that hc_seg_decompress_range runs before it uploads anything. Plain C++, no HIP
+// types: hc_seg.hip includes it, and so does tests/seg_index_check.cpp, which runs it under the
+// sanitizers. Everything here parses untrusted lengths: sums saturate and ranges are compared by
+// subtraction, as in the device scan (seg_open_kernel), whose verdicts these must equal.
+#pragma once
+
+#include <stdint.h>
+#include <string.h>
+
+#include "hcodec.h"
+
+namespace hc_seg_index {
+
+constexpr uint32_t kSegFlags = HC_FLAG_DIFF | HC_FLAG_ADAPT | HC_SEG_CHECK_CRC32;
+const uint8_t kMagic[8] = {0x48, 0x43, 0x53, 0x45, 0x47, 0x31, 0x00, 0xFF};
+
+inline uint64_t align16(uint64_t x) { return (x + 15) & ~15ull; }
+inline uint64_t sat_add(uint64_t a, uint64_t b) { return a + b < a ? ~0ull : a + b; }
+// header and index: 8 bytes of enc_len per segment, and 4 of crc in a checked container
+inline bool checked(uint32_t flags) { return (flags & HC_SEG_CHECK_CRC32) != 0; }
+inline uint64_t index_end(uint64_t n, bool check) { return 48 + (check ? 12 : 8) * n; }
+
+// The cut rule: segment k is raw bytes [k full, k full + (k == n - 1 ? last : full)). n == 0:
+// invalid arguments. No product here overflows: every one is at most raw.
+struct Cuts {
+    uint64_t n, full, last;
+};
+inline Cuts seg_cuts(uint64_t raw, uint64_t seg, bool adapt, uint64_t width)
+{
+    Cuts c{0, 0, 0};
+    if (seg == 0 || (seg & 15u)) return c;
+    if (!adapt) {
+        c.n = raw / seg + (raw % seg != 0);
+        if (c.n == 0) c.n = 1;
+        c.full = seg;
+        c.last = raw - (c.n - 1) * seg;
+        return c;
+    }
+    if (width < 8 || raw % width != 0 || raw / width < 8) return c;
+    // bands of `rows` rows, a multiple of 4 so that every band starts 4-byte aligned; a band
+    // that would leave fewer than 8 rows (too few for a matrix) takes those too
+    const uint64_t h = raw / width;
+    uint64_t rows = (seg / width) & ~3ull;
+    if (rows < 8) rows = 8;
+    const uint64_t q = h / rows, r = h % rows;
+    c.full = rows * width;
+    if (q == 0) {
+        c.n = 1;
+        c.last = raw;
+    } else if (r < 8) {
+        c.n = q;
+        c.last = (rows + r) * width;
+    } else {
+        c.n = q + 1;
+        c.last = r * width;
+    }
+    return c;
+}
+
+// every header rule that needs no index entry (hc_seg_info; the device decoders on their info)
+inline bool info_ok(const hc_seg_info_t &f, uint64_t in_len, Cuts &c)
+{
+    if (in_len < 48) return false;
+    if (f.flags & ~kSegFlags) return false;
+    const bool adapt = (f.flags & HC_FLAG_ADAPT) != 0;
+    if (!adapt && f.width != 0) return false;
+    c = seg_cuts(f.raw_len, f.seg_bytes, adapt, f.width);
+    if (c.n == 0 || c.n != f.n_segments) return false;
+    if (c.n > (in_len - 48) / (checked(f.flags) ? 12 : 8)) return false;  // 48 + 8 n (checked: 12 n) <= in_len
+    // at most 8 symbols per payload byte, and 4 symbols expand to at most 258 bytes
+    if (in_len <= ~0ull / 520 && f.raw_len > 520 * in_len) return false;
+    return true;
+}
+
+inline uint64_t get64(const uint8_t *p)
+{
+    uint64_t v = 0;
+    for (int i = 7; i >= 0; --i) v = (v << 8) | p[i];
+    return v;
+}
+
+// hc_seg_info after its null check: the 48 header bytes against in_len
+inline int parse_header(const uint8_t *in, uint64_t in_len, hc_seg_info_t *info)
+{
+    memset(info, 0, sizeof(*info));
+    if (!in || in_len < 48) return HC_ERR_SEG_HEADER;
+    if (memcmp(in, kMagic, 8) != 0) return HC_ERR_SEG_HEADER;
+    if (in[9] > 1) return HC_ERR_SEG_HEADER;  // the check kind: none or CRC-32
+    for (int i = 10; i < 16; ++i)
+        if (in[i]) return HC_ERR_SEG_HEADER;
+    hc_seg_info_t f;
+    f.flags = in[8] | ((uint32_t)in[9] << 8);
+    f.raw_len = get64(in + 16);
+    f.seg_bytes = get64(in + 24);
+    f.width = get64(in + 32);
+    f.n_segments = get64(in + 40);
+    Cuts c;
+    if (!info_ok(f, in_len, c)) return HC_ERR_SEG_HEADER;
+    *info = f;
+    return HC_OK;
+}
+
+// The segments that hold raw bytes [offset, offset + length), length > 0 inside raw_len: k0 ..
+// k0 + count - 1. The clamp to n - 1 is for an adaptive container whose last band took leftover
+// rows (last > full): bytes past n full belong to it. length == 0: none (k0 0, count 0).
+struct Cover {
+    uint64_t k0, count;
+};
+inline bool range_ok(uint64_t raw_len, uint64_t offset, uint64_t length)
+{
+    return offset <= raw_len && length <= raw_len - offset;
+}
+inline Cover range_cover(const Cuts &c, uint64_t offset, uint64_t length)
+{
+    if (length == 0) return Cover{0, 0};
+    uint64_t k0 = offset / c.full, k1 = (offset + length - 1) / c.full;
+    if (k0 > c.n - 1) k0 = c.n - 1;
+    if (k1 > c.n - 1) k1 = c.n - 1;
+    return Cover{k0, k1 - k0 + 1};
+}
+
+// The index of a container whose header passed info_ok (so the n entries lie inside in_len):
+// HC_OK when the entries tile [align16(index end), in_len) exactly, else HC_ERR_SEG_HEADER.
+// *s0, *s1: the encoded bytes [s0, s1) of the covered segments, from segment k0's first byte to
+// the last byte of segment k0 + count - 1 (count 0: both the first segment's offset).
+inline int index_scan(const uint8_t *in, uint64_t in_len, uint64_t n, bool check, Cover cv, uint64_t *s0,
+                      uint64_t *s1)
+{
+    uint64_t off = align16(index_end(n, check));
+    *s0 = *s1 = off;
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint64_t len = get64(in + 48 + 8 * k);
+        if (len > in_len || off > in_len || len > in_len - off) return HC_ERR_SEG_HEADER;
+        if (k == n - 1 && off + len != in_len) return HC_ERR_SEG_HEADER;  // truncated, or trailing bytes
+        if (cv.count && k == cv.k0) *s0 = off;
+        if (cv.count && k == cv.k0 + cv.count - 1) *s1 = off + len;
+        off = sat_add(off, align16(len));
+    }
+    return HC_OK;
+}
+
+}  // namespace hc_seg_index

@@ -143,6 +143,13 @@ def _load(path):
     L.hc_seg_decompress_work_bound.argtypes = [ctypes.POINTER(SegInfo), u64]
     L.hc_seg_decompress_work_bound.restype = u64
     L.hc_seg_decompress_dev.argtypes = [vp, u64, ctypes.POINTER(SegInfo), vp, u64, vp, vp, vp, vp, u64, vp]
+    L.hc_seg_range_segments.argtypes = [ctypes.POINTER(SegInfo), u64, u64, u64, ctypes.POINTER(u64),
+                                        ctypes.POINTER(u64)]
+    L.hc_seg_decompress_range.argtypes = [u8p, u64, u64, u64, u8p, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    L.hc_seg_decompress_range_work_bound.argtypes = [ctypes.POINTER(SegInfo), u64, u64, u64]
+    L.hc_seg_decompress_range_work_bound.restype = u64
+    L.hc_seg_decompress_range_dev.argtypes = [vp, u64, ctypes.POINTER(SegInfo), u64, u64, vp, u64, vp, vp, vp, vp, u64,
+                                              vp]
     _libs[path] = L
     return L
 
@@ -438,6 +445,61 @@ def seg_decompress_dev(inp, out, out_len, status, bad_segment=None, info=None, s
                                      _dp(work), work.numel(), _stream_handle(stream))
     if rc:
         raise HCodecError(f"hc_seg_decompress_dev failed: {rc}")
+    return work
+
+
+def seg_range_segments(info, in_len, offset, length):
+    """hc_seg_range_segments (host only, no device): (status, first, count) of the segments that
+    hold raw bytes [offset, offset + length) of a container with this SegInfo"""
+    first = ctypes.c_uint64(0)
+    count = ctypes.c_uint64(0)
+    st = lib().hc_seg_range_segments(ctypes.byref(info) if info is not None else None, in_len, offset, length,
+                                     ctypes.byref(first), ctypes.byref(count))
+    return st, first.value, count.value
+
+
+def seg_decompress_range(data, offset, length, full=False, cap=None):
+    """hc_seg_decompress_range: (status, raw bytes [offset, offset + length) of the container);
+    full: (status, bytes, out_len, bad_segment). cap: the output capacity (default: length). Only
+    the header, the index and the covered segments are uploaded."""
+    b, p = _buf(data)
+    if cap is None:
+        cap = length
+    out = ctypes.create_string_buffer(max(int(cap), 1))
+    n = ctypes.c_uint64(0)
+    bad = ctypes.c_uint64(NO_SEGMENT)
+    st = lib().hc_seg_decompress_range(p, len(b), offset, length, ctypes.cast(out, ctypes.c_void_p), cap,
+                                       ctypes.byref(n), ctypes.byref(bad))
+    got = out.raw[:n.value] if st == 0 else b""
+    return (st, got, n.value, bad.value) if full else (st, got)
+
+
+def seg_decompress_range_dev(inp, out, out_len, status, offset, length, bad_segment=None, info=None, stream=None,
+                             work=None, in_len=None, out_cap=None):
+    """hc_seg_decompress_range_dev on CUDA tensors: raw bytes [offset, offset + length) of the
+    container in inp[:in_len] into out[:length] (capacity out_cap, default all of `out`). info as
+    for seg_decompress_dev. A range outside the container's raw_len raises. Returns the workspace."""
+    _check_seg(inp, out, out_len, status, bad_segment)
+    n = inp.numel() if in_len is None else int(in_len)
+    if n > inp.numel():
+        raise ValueError(f"in_len {n} exceeds the {inp.numel()}-byte input tensor")
+    cap = out.numel() if out_cap is None else int(out_cap)
+    if cap > out.numel():
+        raise ValueError(f"out_cap {cap} exceeds the {out.numel()}-byte output tensor")
+    if info is None:
+        head, p = _buf(inp[:min(n, 48)].cpu().numpy().tobytes())
+        info = SegInfo()  # stays all zero when the header does not parse: the call rejects it
+        lib().hc_seg_info(p, n, ctypes.byref(info))
+    need = int(lib().hc_seg_decompress_range_work_bound(ctypes.byref(info), n, offset, length))
+    if work is None:
+        work = _work(need, inp.device)
+    _check_work(work, inp.device, need)
+    rc = lib().hc_seg_decompress_range_dev(_dp(inp), n, ctypes.byref(info), offset, length, _dp(out), cap,
+                                           _dp(out_len), _dp(status),
+                                           ctypes.c_void_p(None) if bad_segment is None else _dp(bad_segment),
+                                           _dp(work), work.numel(), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_seg_decompress_range_dev failed: {rc}")
     return work
 
 

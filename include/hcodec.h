@@ -285,6 +285,88 @@ int hc_seg_decompress_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_
                           uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status,
                           uint64_t *bad_segment, void *work, uint64_t work_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Range decode: raw bytes [offset, offset + length) of a container without decoding the rest.
+ * The cuts are a function of the header, so the segments that hold a range are known before any
+ * payload byte is read; every segment restarts the coder's model, so they decode alone.
+ *
+ * Covered segments. With n, full and last the container's cuts (segment k is raw bytes
+ * [k full, k full + cap_k), cap_k = last for k == n - 1 and full otherwise), a range of
+ * length > 0 covers the segments k0 .. k1, k0 = min(offset / full, n - 1) and
+ * k1 = min((offset + length - 1) / full, n - 1). (The clamp matters in an adaptive container
+ * whose last band took leftover rows: there last > full.) A range of length 0 covers nothing.
+ *
+ * Range check. The range must lie inside raw_len: offset <= raw_len and length <= raw_len -
+ * offset; anything else is HC_ERR_ARG, decided on the host (raw_len is in the host's info). The
+ * empty range is valid at every such offset, the empty range of an empty container included.
+ *
+ * The container-level verdict does not depend on the range: a container that hc_seg_decompress*
+ * answers with HC_ERR_SEG_HEADER (the device header against the caller's copy; the index, all
+ * 8 n bytes of which are still scanned, must tile [align16(48 + 8 n or 12 n), in_len) exactly)
+ * gets that answer for every valid range, the empty one included.
+ *
+ * Status, in this order:
+ *   1  HC_ERR_ARG         null pointers (device call: misaligned buffers)   *out_len, *bad_segment not set
+ *   2  HC_ERR_SEG_HEADER  the header fails                                   0, UINT64_MAX
+ *   3  HC_ERR_ARG         the range is not inside raw_len                    not set
+ *   4  HC_ERR_SEG_HEADER  the index fails                                    0, UINT64_MAX
+ *   5  HC_ERR_DEVICE      host call without a device                         0, UINT64_MAX
+ *   6  HC_ERR_CAPACITY    out_cap < length                                   length, UINT64_MAX
+ *   7  the status of the lowest failing COVERED segment, by hc_seg_decompress's mapping (the
+ *      coder's own status; another length than the cut: HC_ERR_SEG_SIZE; in a checked container
+ *      the right length with another CRC-32: HC_ERR_SEG_CHECK)               0, its container index
+ *   8  HC_OK                                                                 length, UINT64_MAX
+ * A damaged segment outside the range is not noticed: that is the contract, not an accident (a
+ * ranged read neither reads nor decodes such a segment). Every covered segment is decoded whole,
+ * the partially covered first and last ones included, so in a checked container the CRC-32 of
+ * every covered segment is verified.
+ *
+ * Writes. No byte outside out[0 .. length) is written, whatever the status; on a non-zero status
+ * the contents of that range are unspecified. out_cap above length is allowed (and need not
+ * reach raw_len). The range (0, raw_len) gives exactly what hc_seg_decompress* gives: status,
+ * bytes, *out_len and *bad_segment.
+ * ------------------------------------------------------------------------------------- */
+
+/* Host only, no device. The segments that hold raw bytes [offset, offset + length) of a container
+ * with this info: *first, *count (count 0 when length is 0). HC_OK, or HC_ERR_ARG (null pointer,
+ * an info that fails hc_seg_info's rules for in_len, offset > raw_len, length > raw_len - offset). */
+int hc_seg_range_segments(const hc_seg_info_t *info, uint64_t in_len, uint64_t offset, uint64_t length,
+                          uint64_t *first, uint64_t *count);
+
+/* Host buffers, synchronous: raw bytes [offset, offset + length) of the container into out[0 .. length).
+ * The header and the index are checked on the host (HC_ERR_SEG_HEADER needs no device); only the
+ * header, the index and the encoded bytes of the covered segments are uploaded, the device buffers
+ * are sized by those and by length, and only length bytes come back. bad_segment may be NULL. */
+int hc_seg_decompress_range(const uint8_t *in, uint64_t in_len, uint64_t offset, uint64_t length,
+                            uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment);
+
+/* Device buffers, asynchronous on `stream`, under the rules of hc_seg_decompress_dev: in, out and
+ * work 16-byte aligned; out_len, status and bad_segment DEVICE pointers; no allocation, no host
+ * synchronisation, no host read of device memory. `in` holds the whole container (of which the
+ * header, the index and the covered segments are read). An info that fails hc_seg_info's rules
+ * gets HC_ERR_SEG_HEADER as the device status; a range outside raw_len and work_bytes below the
+ * bound are HC_ERR_ARG.
+ *
+ * All covered segments decode in one launch. One that lies wholly inside the range decodes in
+ * place at out + (k full - offset) when offset is a multiple of 4 (the coders need a 4-byte
+ * aligned output, and full is a multiple of 4). Every other one is staged: it decodes into a slot
+ * of align16(max(full, last)) bytes inside `work`, and its covered part is then copied to out at
+ * any byte alignment. So the bound holds, for an offset that is a multiple of 4, one slot for each
+ * partly covered edge segment (at most two; none when the range starts and ends on cuts), and one
+ * slot per covered segment otherwise; plus 44 bytes (checked: 48) per covered segment, not per
+ * segment of the container, 24 per slot, and for -a the adaptive batch workspace of the covered
+ * segments (hc_adapt_decompress_work_bound(in_len, their raw bytes, their count)). For the range
+ * (0, raw_len) of a non-empty container that is hc_seg_decompress_work_bound's value, and the call
+ * launches what hc_seg_decompress_dev launches.
+ * hc_seg_decompress_range_work_bound: 0 for a null info or a range outside raw_len, 16 for an
+ * info that fails the rules (as hc_seg_decompress_work_bound). */
+uint64_t hc_seg_decompress_range_work_bound(const hc_seg_info_t *info, uint64_t in_len,
+                                            uint64_t offset, uint64_t length);
+int hc_seg_decompress_range_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info,
+                                uint64_t offset, uint64_t length, uint8_t *out, uint64_t out_cap,
+                                uint64_t *out_len, int32_t *status, uint64_t *bad_segment,
+                                void *work, uint64_t work_bytes, void *stream);
+
 /* CRC-32 (zlib's crc32: reflected polynomial 0xEDB88320, init and final xor 0xFFFFFFFF) of
  * n_ranges byte ranges, the kernel behind the checked container: crc[i] of in[in_offs[i] ..
  * +lens[i]). DEVICE pointers, asynchronous on `stream`; any alignment, any length (0: crc 0), any

@@ -12,6 +12,12 @@ on both sides), median of the repeats after warm-up. Prints one JSON line.
                                              hc_seg_compress2 with HC_SEG_CHECK_CRC32) beside each
                                              unchecked figure
   scripts/seg_bench.py --no-whole --sizes 65536   the segmented calls alone, at the sizes named
+  scripts/seg_bench.py --range               ranged reads (hc_seg_decompress_range, and
+                                             hc_seg_decompress_range_dev under HIP events) against
+                                             hc_seg_decompress plus a slice: 4 KiB inside one segment,
+                                             1 MiB at a multiple of 4 and the same 1 MiB one byte on
+                                             (every covered segment staged); --big adds a 16384x16384
+                                             photo (4096 segments of 64 KiB)
   scripts/seg_bench.py --trace-run           a few segmented calls only, to be run under
                                              `rocprofv3 --kernel-trace --stats -- python ...`
   scripts/seg_bench.py --glue-from STATS.csv adds the glue kernels' share of device time, read
@@ -35,14 +41,14 @@ SIDE = 4096
 MODES = {"-m": (1, 0), "-a -m": (1, 1), "-a": (0, 1)}
 SIZES = (16384, 65536, 262144)
 GLUE = ("seg_plan_kernel", "seg_seal_kernel", "seg_gather_kernel", "seg_open_kernel", "seg_close_kernel",
-        "crc32_kernel")
+        "crc32_kernel", "pack_kernel")
 
 
-def photo():
+def photo(side=SIDE):
     import torch
-    n = SIDE * SIDE
+    n = side * side
     raw = torch.empty(n, dtype=torch.uint8, device="cuda")
-    hc.synth_batch("photo", 0, 1, SIDE, SIDE, raw, n)
+    hc.synth_batch("photo", 0, 1, side, side, raw, n)
     torch.cuda.synchronize()
     return raw.cpu().numpy().tobytes()
 
@@ -105,6 +111,100 @@ def timed(fn, warmup, reps):
     return round(statistics.median(ts), 3), round(min(ts), 3), round(max(ts), 3)
 
 
+def align16(x):
+    return (x + 15) & ~15
+
+
+def range_bench(raw, side, diff, adapt, seg, reps, device):
+    """one container: the three ranges through the host call (against hc_seg_decompress plus a
+    slice) and, with `device`, through the device call under HIP events"""
+    import struct
+    import torch
+    L = hc.lib()
+    st, enc = hc.seg_compress(raw, bool(diff), bool(adapt), side, seg)
+    assert st == 0, st
+    st, info = hc.seg_info(enc)
+    n = info.n_segments
+    lens = struct.unpack_from(f"<{n}Q", enc, 48)
+    offs, o = [], align16(48 + 8 * n)
+    for m in lens:
+        offs.append(o)
+        o = align16(o + m)
+    src = ctypes.cast(ctypes.c_char_p(enc), ctypes.c_void_p)
+    whole = ctypes.create_string_buffer(len(raw))
+    k = ctypes.c_uint64(0)
+
+    def full_then_slice(o, m):
+        rc = L.hc_seg_decompress(src, len(enc), ctypes.cast(whole, ctypes.c_void_p), len(raw), ctypes.byref(k), None)
+        assert rc == 0, rc
+        return whole[o:o + m]
+
+    full_work = int(L.hc_seg_decompress_work_bound(ctypes.byref(info), len(enc)))
+    res = {"bytes": len(enc), "segments": n,
+           "whole": {"uploaded": len(enc), "device_bytes": len(enc) + 16 + len(raw) + 16 + full_work + 32}, "ranges": {}}
+    mid = (len(raw) // 2) & ~65535
+    ranges = {"4KiB": (mid + 8192, 4096), "1MiB": (mid + 4096, 1 << 20), "1MiB+1": (mid + 4097, 1 << 20)}
+    for name, (o, m) in ranges.items():
+        st, first, count = hc.seg_range_segments(info, len(enc), o, m)
+        assert st == 0 and count
+        span = offs[first + count - 1] + lens[first + count - 1] - offs[first]
+        work = int(L.hc_seg_decompress_range_work_bound(ctypes.byref(info), len(enc), o, m))
+        if adapt:  # the host call sizes the adaptive workspace by the span, not by the container
+            assert first + count < n  # (no range here reaches the last segment)
+            covered_raw = count * full_bytes(seg, adapt, side)
+            work += int(L.hc_adapt_decompress_work_bound(span, covered_raw, count)) - int(
+                L.hc_adapt_decompress_work_bound(len(enc), covered_raw, count))
+        out = ctypes.create_string_buffer(m)
+
+        def ranged():
+            rc = L.hc_seg_decompress_range(src, len(enc), o, m, ctypes.cast(out, ctypes.c_void_p), m, ctypes.byref(k), None)
+            assert rc == 0 and k.value == m, rc
+
+        r = {"offset": o, "length": m, "covered": count, "range_ms": timed(ranged, 2, reps),
+             "whole_and_slice_ms": timed(lambda: full_then_slice(o, m), 2, reps),
+             "uploaded": align16(48 + 8 * n) + span,
+             "device_bytes": align16(48 + 8 * n) + span + 16 + m + 16 + work + 32}
+        assert out.raw == raw[o:o + m] and full_then_slice(o, m) == raw[o:o + m]
+        r["speedup"] = round(r["whole_and_slice_ms"][0] / r["range_ms"][0], 2)
+        res["ranges"][name] = r
+    if device:
+        import numpy as np
+        host = np.zeros(align16(len(enc)), dtype=np.uint8)
+        host[:len(enc)] = np.frombuffer(enc, dtype=np.uint8)
+        inp = torch.from_numpy(host).cuda()
+        dout = torch.empty(len(raw), dtype=torch.uint8, device="cuda")
+        olen = torch.zeros(1, dtype=torch.int64, device="cuda")
+        stt = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+        def events(fn):
+            ts = []
+            for i in range(2 + reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                assert int(stt.item()) == 0
+                if i >= 2:
+                    ts.append(e0.elapsed_time(e1))
+            return round(statistics.median(ts), 3), round(min(ts), 3), round(max(ts), 3)
+
+        work = hc.seg_decompress_dev(inp, dout, olen, stt, info=info, in_len=len(enc))
+        res["whole"]["device_ms"] = events(lambda: hc.seg_decompress_dev(inp, dout, olen, stt, info=info, in_len=len(enc),
+                                                                         work=work))
+        for name, (o, m) in ranges.items():
+            w = hc.seg_decompress_range_dev(inp, dout, olen, stt, o, m, info=info, in_len=len(enc), out_cap=m)
+            res["ranges"][name]["device_ms"] = events(lambda: hc.seg_decompress_range_dev(
+                inp, dout, olen, stt, o, m, info=info, in_len=len(enc), out_cap=m, work=w))
+            assert dout[:m].cpu().numpy().tobytes() == raw[o:o + m]
+    return res
+
+
+def full_bytes(seg, adapt, width):
+    """raw bytes of every segment but the last (the cut rule of include/hcodec.h)"""
+    return max(8, (seg // width) & ~3) * width if adapt else seg
+
+
 def glue_share(path):
     glue = total = 0
     per = {}
@@ -130,9 +230,31 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--no-whole", action="store_true")
     ap.add_argument("--sizes", type=int, nargs="+", default=list(SIZES))
+    ap.add_argument("--range", action="store_true")
+    ap.add_argument("--big", action="store_true")
     a = ap.parse_args()
     if not hc.device_ok():
         sys.exit("seg_bench.py needs a gfx950 device: " + hc.device_info())
+    if a.range:
+        raw = photo()
+        if a.trace_run:
+            for diff, adapt in ((1, 0), (1, 1)):
+                range_bench(raw, SIDE, diff, adapt, 65536, 3, False)
+            return
+        res = {"input": f"synthetic photo {SIDE}x{SIDE} ({len(raw)} bytes)", "timing":
+               "range_ms, whole_and_slice_ms: host clock around each synchronous host-buffer call (copies included); "
+               "device_ms: HIP events around the device call; median [min, max] ms of %d" % a.reps, "cases": {}}
+        for name, (diff, adapt) in (("-m", (1, 0)), ("-a -m", (1, 1))):
+            for seg in (16384, 65536):
+                res["cases"][f"{name} {seg}"] = range_bench(raw, SIDE, diff, adapt, seg, a.reps, True)
+        if a.big:
+            raw = photo(4 * SIDE)
+            res["big_input"] = f"synthetic photo {4 * SIDE}x{4 * SIDE} ({len(raw)} bytes)"
+            res["cases"]["big -m 65536"] = range_bench(raw, 4 * SIDE, 1, 0, 65536, a.reps, True)
+        if a.glue_from:
+            res["glue"] = glue_share(a.glue_from)
+        print(json.dumps(res))
+        return
     b = Buffers(photo())
     if a.trace_run:
         for diff, adapt in MODES.values():
