@@ -39,6 +39,11 @@ namespace hc {
 #if defined(HC_PROF) && !defined(HC_DEBUG_HOOKS)
 #define HC_DEBUG_HOOKS 1
 #endif
+// the most codes one decoder batch step takes (a multiple of 4 up to 24; described with the
+// decoder's other knobs below)
+#ifndef HC_DEC_PACK
+#define HC_DEC_PACK 16
+#endif
 #ifdef HC_DEBUG_HOOKS
 // when non-null, every FGK wave records (start, end, HW_ID | XCC_ID << 16) at [3 * stream]
 // (scripts/residency.py measures how many waves share each SIMD); hc_debug_set_trace
@@ -57,7 +62,7 @@ static uint32_t g_enc_tab = 0;
 static uint32_t g_dec_small = 0;
 // the most codes one decoder batch step takes (Dec::decode_batch; hc_debug_set_dec_pack: 1, 7 or
 // HC_DEC_PACK)
-__device__ uint32_t g_dec_pack = 16;
+__device__ uint32_t g_dec_pack = HC_DEC_PACK;
 __device__ __forceinline__ uint32_t dec_pack_max(uint32_t k) { return min(k, (uint32_t)__builtin_amdgcn_readfirstlane(g_dec_pack)); }
 // the most symbols one regular encoder batch step takes (code_all_batch; hc_debug_set_enc_pack: 1,
 // 7 or HC_ENC_PACK)
@@ -219,7 +224,7 @@ static_assert(HC_ENC_PACK >= 1 && HC_ENC_PACK <= 16, "a step's symbols are the l
 #ifndef HC_ENC_HANDOFF_LEVEL
 #define HC_ENC_HANDOFF_LEVEL 0
 #endif
-// decoder (narrow and wide layouts): HC_DEC_BATCH != 0: up to HC_DEC_PACK (4, 8, 12 or 16) codes
+// decoder (narrow and wide layouts): HC_DEC_BATCH != 0: up to HC_DEC_PACK (4, 8, ... 24) codes
 // per step, packed by bit offset (one lane per code bit), from one read of the level tables at
 // every bit offset and one tentative commit (Dec::decode_batch; HC_DEC_BATCH 0: the one-symbol
 // loop only). Measured on the earlier layout of nine lanes per code, C5 decode: one-symbol loop
@@ -229,8 +234,33 @@ static_assert(HC_ENC_PACK >= 1 && HC_ENC_PACK <= 16, "a step's symbols are the l
 #ifndef HC_DEC_BATCH
 #define HC_DEC_BATCH 7
 #endif
-#ifndef HC_DEC_PACK
-#define HC_DEC_PACK 16
+// HC_DEC_TOPUP 1: a batch step works on 64 true window bits -- the top 64 - nwin bits of the next
+// unread word are peeked into the window before the step (BitSource::peek), so a step takes codes
+// up to bit 62 whatever the window held; 0: the window's own 32..64 bits bound the step (tests/
+// fgk_topup_model.py; photo -c -m: 8-15 % fewer steps, C5 decode -3 %; with the full window 20 and
+// 24 codes a step take fewer steps still but send more symbols to the one-symbol step, and measured
+// slower than 16: DESIGN.md section 7)
+// The parent's decoder (round 9) is -DHC_DEC_TOPUP=0 -DHC_DEC_NEXTW=0: HC_DEC_NEXTW below also
+// changes every refill of the one-symbol loop, so the A/B of the shipped build against that one
+// measures both together.
+// HC_DEC_TOPUP_SMALL 1: the small-alphabet launch (streams under 2.5 payload bits per symbol: both
+// Dec::decode_small and its copy of decode_batch) takes the full window too. Off: its 15 or 16
+// symbols of ~1.7 bits (grad -c -m) never reach the end of the window's own bits, so the peek and
+// the refill test only cost (grad decode 1.12 -> 1.15 ms with it on)
+#ifndef HC_DEC_TOPUP
+#define HC_DEC_TOPUP 1
+#endif
+#ifndef HC_DEC_TOPUP_SMALL
+#define HC_DEC_TOPUP_SMALL 0
+#endif
+static_assert(HC_DEC_TOPUP || !HC_DEC_TOPUP_SMALL, "the small-alphabet step's top-up needs HC_DEC_TOPUP");
+// HC_DEC_NEXTW 1: the next unread word is kept in a scalar register (BitSource::nw, read in
+// next_word() where refill() read its lane before): a peek is a shift and an OR, and a refill no
+// longer waits for a lane read. Measured against 0 (the word read from its lane at the peek and at
+// the refill): C3 decode 154.7 -> 152.1 ms, noise 161.9 -> 160.6, grad 1.160 -> 1.147, C5 356.0 ->
+// 356.8 (the flat alphabets wait on dependencies, C5 on issue slots)
+#ifndef HC_DEC_NEXTW
+#define HC_DEC_NEXTW 1
 #endif
 #ifndef HC_DEC_EXIT8
 #define HC_DEC_EXIT8 1
@@ -2177,6 +2207,12 @@ struct BitSource {
     uint32_t ridx;
     uint64_t win;  // upcoming bits, MSB-aligned
     uint32_t nwin; // valid bits in win
+#if HC_DEC_NEXTW
+    uint32_t nw;  // chunk[ridx], the next unread word, in a scalar register: a peek reads no lane
+    __device__ __forceinline__ uint32_t word() const { return nw; }
+#else
+    __device__ __forceinline__ uint32_t word() const { return lane_read(chunk, ridx); }
+#endif
 
     __device__ __forceinline__ void next_word()
     {
@@ -2186,11 +2222,30 @@ struct BitSource {
             nxt = buf_load(rs, cbase + 256 + lane * 4);
             ridx = 0;
         }
+#if HC_DEC_NEXTW
+        nw = lane_read(chunk, ridx);
+#endif
+    }
+    // the window with the bits below its nwin >= 32 valid ones filled from the next unread word:
+    // 64 true bits. No state changes: refill() ORs the same word at the same place later.
+    __device__ __forceinline__ uint64_t peek() const
+    {
+        return win | (uint32_t)((uint64_t)word() >> (nwin - 32));
+    }
+    // a batch step took sj of the n0 valid bits of w (peek()'s value): when sj > n0 the bits past
+    // n0 come off the peeked word, which refill() pushes with those bits shifted out (nwin < 0 as
+    // a signed value: its shift is 32 - nwin <= 63); 1..31 bits are valid after it, and every
+    // call site tests nwin <= 32 before the window is read again
+    __device__ __forceinline__ void take_peeked(uint64_t w, uint32_t n0, uint32_t sj)
+    {
+        win = w << sj;
+        nwin = n0 - sj;
+        if ((int32_t)nwin < 0) refill();
     }
     // push the next 32 bits (needs nwin <= 32)
     __device__ __forceinline__ void refill()
     {
-        const uint32_t w = lane_read(chunk, ridx);
+        const uint32_t w = word();
         win |= (uint64_t)w << (32 - nwin);
         nwin += 32;
         next_word();
@@ -2446,6 +2501,9 @@ struct Dec {
         in.chunk = __builtin_bswap32(hdr);
         in.nxt = buf_load(rin, 256 + lane * 4);
         in.ridx = 2;
+#if HC_DEC_NEXTW
+        in.nw = lane_read(in.chunk, 2);
+#endif
         in.win = 0;
         in.nwin = 0;
         in.refill();  // word 2: flags byte + first payload bits
@@ -2599,6 +2657,8 @@ struct Dec {
     }
 
 #if HC_DEC_BATCH
+    // the batch steps of this launch work on 64 true window bits (BitSource::peek)
+    static constexpr bool kTopUp = HC_DEC_TOPUP && (!kSmall || HC_DEC_TOPUP_SMALL);
     // Batched hot path (narrow and wide layouts; model: tests/fgk_pack_model.py decode_packed).
     // Between swaps and splits the tree's shape -- and with it every code -- is fixed, and the
     // update of a symbol whose levels all pass the leader test only adds 1 along its root path.
@@ -2625,10 +2685,11 @@ struct Dec {
     __device__ __forceinline__ bool decode_batch(Idx i0, Idx &i, Idx i1)
     {
         constexpr uint32_t kPackMax = HC_DEC_PACK;  // codes per step
-        static_assert(kPackMax % 4 == 0 && kPackMax >= 4 && kPackMax <= 16, "chain chunks of four codes");
+        static_assert(kPackMax % 4 == 0 && kPackMax >= 4 && kPackMax <= 24, "chain chunks of four codes");
         constexpr uint64_t kL63 = 1ull << 63;
-        const uint64_t w0 = in.win;
-        const uint32_t n0 = in.nwin;  // >= 33
+        const uint32_t n0 = in.nwin;  // >= 32 (32: after a step that took the whole window)
+        const uint64_t w0 = kTopUp ? in.peek() : in.win;  // kTopUp: 64 true bits
+        const uint32_t lim = kTopUp ? 63u : min(n0, 63u);
         const uint32_t l8 = lds_off16(&fgk.T.lvl[254]);  // level 8
         // lane o: the depth of a code that starts o bits into the window (its level-8 entry)
         const uint32_t dep = opaque(*(const lds_u16 *)(size_t)(l8 + 2 * (uint32_t)((w0 << lane) >> 56))) >> 10;
@@ -2641,13 +2702,12 @@ struct Dec {
             return false;
         }
         // the chain of code starts: sv lane j = S_j, the bits before code j (255: no such code).
-        // Four codes per exit test; a code is taken only if it ends within the window's valid
-        // bits and within bit 62, so the chain ends once S passes lim. Past bit 63 the depths
+        // Four codes per exit test; a code is taken only if it ends within bit 62 (HC_DEC_TOPUP 0:
+        // and within the window's valid bits), so the chain ends once S passes lim. Past bit 63 the depths
         // read are another offset's (the lane select wraps): S still grows, so those starts
         // stay above lim.
         // (measured and dropped on the 7 x 9 layout: the chain by pointer doubling, C5 decode
         // +0.8 %)
-        const uint32_t lim = min(n0, 63u);
         uint32_t sv = lane == 0 ? 0u : 255u;
         sv = writelane(sv, S, 1);
 #pragma unroll
@@ -2709,8 +2769,12 @@ struct Dec {
         HC_CNT(1);
         if (jf < jmax) HC_CNT(2);
         if (nl && ff1(nl) == ff1(fm)) HC_CNT(5);
-        in.win = w0 << sj;
-        in.nwin = n0 - sj;
+        if constexpr (kTopUp) {
+            in.take_peeked(w0, n0, sj);
+        } else {
+            in.win = w0 << sj;
+            in.nwin = n0 - sj;
+        }
         i += jf;
         bsym += jf;
         ++btry;
@@ -2744,8 +2808,8 @@ struct Dec {
         const uint32_t l4 = lds_off16(&fgk.T.lvl[14]);  // level 4
         const uint32_t sscb = lds_off(&fgk.T.scratch[0]) + 4 * ln;
         const uint32_t mkb = lds_off(&fgk.T.smark[0]);
-        const uint64_t w0 = in.win;
-        const uint32_t n0 = in.nwin;  // >= 33: symbols 0..7 always fit
+        const uint32_t n0 = in.nwin;  // >= 32: symbols 0..7 always fit
+        const uint64_t w0 = kTopUp ? in.peek() : in.win;  // kTopUp: 64 true bits, all 15 symbols (<= 60 bits) fit
         // lane o: the depth of a code that starts o bits into the window (4 when deeper)
         const uint32_t dep = opaque(*(const lds_u16 *)(size_t)(l4 + 2 * (uint32_t)((w0 << ln) >> 60))) >> 10;
         // each lane's own code start by a select per chain step (measured: grad decode 1.172 ->
@@ -2758,7 +2822,7 @@ struct Dec {
             S += lane_read(dep, S);
         }
         sv = writelane(sv, S, kSK);
-        const uint32_t nval = __builtin_popcountll(ballot(sv <= n0) & (((1ull << kSK) - 1) << 1));
+        const uint32_t nval = kTopUp ? kSK : (uint32_t)__builtin_popcountll(ballot(sv <= n0) & (((1ull << kSK) - 1) << 1));
         const uint32_t jmax = min(nval, (uint32_t)(i1 - i));
         const uint32_t ent = opaque(*(const lds_u16 *)(size_t)(bvb + (((uint32_t)((w0 << sg) >> 32) >> (28 + bl)) << 1)));
         uint32_t pos = ent & 1023u;
@@ -2790,8 +2854,12 @@ struct Dec {
         HC_CNT(1);
         if (jf < jmax) HC_CNT(2);
         const uint32_t sj = lane_read(sv, jf);
-        in.win = w0 << sj;
-        in.nwin = n0 - sj;
+        if constexpr (kTopUp) {
+            in.take_peeked(w0, n0, sj);
+        } else {
+            in.win = w0 << sj;
+            in.nwin = n0 - sj;
+        }
         i += jf;
         bsym += jf;
         ++btry;
@@ -3093,7 +3161,7 @@ extern "C" int hc_debug_set_dec_pack(uint32_t max)
     // the most codes a decoder batch step takes in every later FGK launch on the current device
     // (a device variable, like the window: other devices keep theirs): 1, 7, or anything else
     // for the build's HC_DEC_PACK
-    uint32_t k = max == 1 || max == 7 ? max : 16u;
+    uint32_t k = max == 1 || max == 7 ? max : (uint32_t)HC_DEC_PACK;
     return hipMemcpyToSymbol(HIP_SYMBOL(hc::g_dec_pack), &k, sizeof(k)) == hipSuccess ? 0 : HC_ERR_DEVICE;
 }
 
