@@ -195,6 +195,12 @@ constexpr uint32_t kInsertDepth = HC_INSERT_DEPTH;
 #endif
 // encoder: a miss chases this many levels, then looks the position reached up in the path cache
 constexpr uint32_t kProbe = HC_PROBE;
+// HC_CHASE_GROUP n > 0: the path-cache encoder's miss chase climbs without a per-level root test:
+// levels 0..kProbe as one group, then n levels between two tests (Fgk::chase_grouped). 0: the
+// per-level climb (Fgk::chase), which the table-mode encoder and the decoder keep either way.
+#ifndef HC_CHASE_GROUP
+#define HC_CHASE_GROUP 4
+#endif
 constexpr uint32_t kRow = 16;       // u16 per cache entry
 // 1: path-cache streams (narrow and wide layouts) code cached symbols up to HC_ENC_PACK (1..16)
 // at a time, packed by path depth (code_all_batch). A symbol's depth and its code record both
@@ -250,6 +256,21 @@ static_assert(HC_ENC_PACK >= 1 && HC_ENC_PACK <= 16, "a step's symbols are the l
 #ifndef HC_DEC_TOPUP
 #define HC_DEC_TOPUP 1
 #endif
+// HC_DESC_GROUP 1: the descent of a code longer than the level tables reach (Dec::finish_symbol)
+// takes its first levels in groups with one inner test a group; HC_DESC_SCHED lists the levels
+// (counted from where the descent starts) after which the test happens, the last one being the
+// levels run this way before the per-level loop takes over. 0: the per-level loop alone.
+// (Measured: a test after every level, {1, 2, ..., 8}, fewer instructions in the model's count, is
+// no faster and its times spread wider: DESIGN.md section 7.)
+#ifndef HC_DESC_GROUP
+#define HC_DESC_GROUP 1
+#endif
+#ifndef HC_DESC_SCHED
+#define HC_DESC_SCHED {1, 4, 5, 6, 8}
+#endif
+constexpr uint32_t kDescSched[] = HC_DESC_SCHED;
+constexpr uint32_t kDescLevels = kDescSched[sizeof(kDescSched) / sizeof(kDescSched[0]) - 1];
+static_assert(kDescLevels <= 24, "the grouped levels take their bits from the window's high word");
 #ifndef HC_DEC_TOPUP_SMALL
 #define HC_DEC_TOPUP_SMALL 0
 #endif
@@ -795,12 +816,86 @@ struct Fgk {
         return kWide ? uni(T.up[x]) : (uni((uint32_t)T.wt[x]) & 1023u);
     }
 
+#if HC_CHASE_GROUP
+    // chase() of the path-cache encoder with the levels climbed back to back (parent read, mask,
+    // next address) and the root tested once per group: level k's position goes straight into
+    // lane k (a select on a one-bit scalar mask), so the path arrives bottom-up. The first group
+    // is levels 0..kProbe, where the path cache is probed as in chase(); the groups after a failed
+    // probe are HC_CHASE_GROUP levels each. A climb that passes the root stays in the tree: the
+    // root's parent field (narrow) and up[kRoot] (wide / huge) are 0 and never written, and
+    // position 0 holds 0 or a real node's parent, so every position read is <= kRoot. The depth is
+    // the first lane holding kRoot (the lanes not yet written hold it too); the lanes from there
+    // on are set to kRoot. (tests/fgk_climb_model.py: Climb)
+    __device__ __forceinline__ uint32_t chase_grouped(uint32_t s0, uint32_t &pv)
+    {
+        constexpr uint32_t kGroup = HC_CHASE_GROUP;
+        static_assert(kProbe < 63 && (63 - kProbe) % kGroup == 0, "the groups end at lane 63");
+        uint32_t s = vreg(s0);  // per-level work on the VALU (see vreg)
+        uint32_t tv = kRoot;    // lane k: level k
+#pragma unroll
+        for (uint32_t i = 0; i < kProbe; ++i) {
+            tv = sel(1ull << i, s, tv);
+            s = kWide ? (uint32_t)T.up[s] : ((uint32_t)T.wt[s] & 1023u);
+        }
+        tv = sel(1ull << kProbe, s, tv);
+        uint32_t d = ff1(ballot(tv == kRoot));
+        if (d > kProbe) {
+            // s: level kProbe, below the root. A cached path through it (rows stay valid paths)
+            // gives the rest of the climb at once
+            constexpr uint64_t kLevels = 0x0FFF0FFF0FFF0FFFull;
+            uint32_t q[kSlots / 4];
+            uint64_t m[kSlots / 4];
+#pragma unroll
+            for (uint32_t r = 0; r < kSlots / 4; ++r) q[r] = T.pc[64 * r + lane];
+#pragma unroll
+            for (uint32_t r = 0; r < kSlots / 4; ++r) m[r] = ballot(q[r] == s) & kLevels;
+            const uint64_t m01 = m[0] | m[1], m23 = m[2] | m[3];
+            if (m01 | m23) {
+                // the first hit: entry e, level lv of its row
+                const uint32_t r = m01 ? (m[0] ? 0u : 1u) : (m[2] ? 2u : 3u);
+                const uint32_t b = ff1(r == 0 ? m[0] : r == 1 ? m[1] : r == 2 ? m[2] : m[3]);
+                const uint32_t e = 4 * r + (b >> 4), lv = b & 15u;
+                // lane j >= kProbe: level j = the row's level lv + j - kProbe (kRoot from the
+                // row's depth on, and past its 12 levels)
+                const uint32_t idx = lv + lane - kProbe;
+                const uint32_t rv = T.pc[e * kRow + min(idx, kRow - 1)];
+                const uint32_t drow = uni(T.pc[e * kRow + kSlotDepth + 1]) & 31u;
+                pv = lane < kProbe ? tv : (idx < kSlotDepth ? rv : kRoot);
+                return kProbe + drow - lv;
+            }
+            uint64_t mk = 1ull << kProbe;  // the lane of the last level recorded
+            uint32_t nx = kProbe + 1;      // the next lane
+#pragma unroll 1
+            do {  // fixed trip bound: the lanes
+#pragma unroll
+                for (uint32_t i = 0; i < kGroup; ++i) {
+                    s = kWide ? (uint32_t)T.up[s] : ((uint32_t)T.wt[s] & 1023u);
+                    mk <<= 1;
+                    tv = sel(mk, s, tv);
+                }
+                nx += kGroup;
+                d = ff1(ballot(tv == kRoot));
+            } while (min(d, 63u) >= nx);  // (nx ends at 64)
+        }
+        // no root within 63 levels (parents sit above children, so this only bounds a bug):
+        // d = 0xFFFFFFFF
+        bad |= d >> 6;
+        pv = sel(below_mask(d), tv, kRoot);
+        return min(d, 64u);
+    }
+#endif
+
     // Encoder: the path from position s to the root, BEFORE the update (the code of
     // huffman.cpp:136-155): the position of level k (0 = s) goes to lane k; returns the levels.
     // Each level enters at lane 0 by a DPP wave shift (lane 0 keeps the new position), so the
     // path arrives top-down; one permute turns it bottom-up at the end.
     __device__ __forceinline__ uint32_t chase(uint32_t s0, uint32_t &pv)
     {
+#if HC_CHASE_GROUP
+        // (the small-alphabet launch keeps the per-level climb: its trees are rarely deeper than
+        // the grouped climb's first kProbe levels, which always run)
+        if constexpr (!kTabs && !kSmall) return chase_grouped(s0, pv);
+#endif
         int32_t km = -64;       // levels - 64
         uint32_t s = vreg(s0);  // per-level work on the VALU (see vreg)
         uint32_t td = kRoot;    // lane j: level k - 1 - j
@@ -2595,8 +2690,63 @@ struct Dec {
             if (in.nwin <= 32) in.refill();
             uint64_t w = in.win;
             uint32_t d0 = depth, lim = min(depth + in.nwin, 63u);
+#if HC_DESC_GROUP
+            bool ended = false;
+            // The first kDescLevels levels in groups (kDescSched: the levels after which the inner
+            // test happens; tests/fgk_climb_model.py chooses it), when the window holds that many
+            // bits. The bits come from a VGPR copy of the window's high word at compile-time
+            // offsets: a level is the bit, the child index, its record into the lane of its depth
+            // and the body read, whose word goes into the same lane of bq -- no window shift, depth
+            // counter or stop arithmetic per level -- and a group ends with one ballot of bq's
+            // inner bits. The first level whose body is not inner ends the code (lanes not written
+            // count as inner); the levels below it read only in-range garbage ((body & 255) * 2 +
+            // bit <= 511), their lanes fall to kRoot in the turn below, and no bit past that level
+            // is consumed. A group of one level tests the body as read and ends in place.
+            // (Measured and dropped: streams whose batch steps are off -- flat alphabets, whose long
+            // codes are one level below the tables -- kept on the per-level loop by a test of
+            // batch_on here: noise decoded 1 % slower with it)
+            if (depth + kDescLevels <= lim) {
+                const uint32_t wv = vreg((uint32_t)(w >> 32));  // nwin > 32 >= kDescLevels
+                uint32_t bq = kInner;
+                uint64_t mk = 1ull << (63 - depth);  // the lane of the level reached next
+                uint64_t ni = 0;
+                uint32_t k = 0, de = depth + kDescLevels;
+#pragma unroll
+                for (uint32_t g = 0; g < sizeof(kDescSched) / sizeof(kDescSched[0]); ++g) {
+                    const bool one = kDescSched[g] == k + 1;  // a one-level group: xv and bv are its end
+#pragma unroll
+                    for (; k < kDescSched[g]; ++k) {
+                        const uint32_t bit = (wv >> (31 - k)) & 1u;
+                        xv = ((bv << 1) & 0x1FEu) | bit;  // child pair * 2 + bit
+                        pt = sel(mk, xv, pt);
+                        bv = opaque(*(const lds_u16 *)(size_t)(bbase + 2 * xv));
+                        if (!one) bq = sel(mk, bv, bq);  // (a level that goes on was inner, as bq starts)
+                        mk >>= 1;
+                    }
+                    if (one) {
+                        if (!ballot(bv & kInner)) {
+                            de = depth + k;
+                            ended = true;
+                            break;
+                        }
+                    } else if ((ni = ballot(!(bq & kInner))) != 0) {
+                        const uint32_t le = 63u - (uint32_t)__builtin_clzll(ni);  // the highest lane: the first such level
+                        de = 64u - le;
+                        xv = vreg(lane_read(pt, le));
+                        bv = vreg(lane_read(bq, le));
+                        ended = true;
+                        break;
+                    }
+                }
+                w <<= de - depth;
+                depth = de;
+            }
+#pragma unroll 1
+            while (!ended) {
+#else
 #pragma unroll 1
             for (;;) {
+#endif
                 uint64_t inner;
 #pragma unroll 1
                 do {
