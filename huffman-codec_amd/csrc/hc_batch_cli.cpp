@@ -13,13 +13,13 @@
 // "FILE: <the reference's message>"; the exit code is the first failing status (0: all ok).
 //
 // -s BYTES with -c writes every FILE.huf as a segmented container (HCSEG1, hcodec.h) of BYTES-byte
-// segments (0: the default size), one hc_seg_compress2 call per file; -k (only with -s) adds a
-// CRC-32 per segment. -d tells containers from plain streams by their first 8 bytes and sends them
-// through hc_seg_decompress_alloc, which verifies the checksums of a container that has them; a
-// failing segment reports "FILE: segment K: <message>".
+// segments (0: the default size), all files in one hc_seg_compress_host_batch call; -k (only with
+// -s) adds a CRC-32 per segment. -d tells containers from plain streams by their first 8 bytes and
+// sends them, all in one call, through hc_seg_decompress_host_batch, which verifies the checksums of
+// a container that has them; a failing segment reports "FILE: segment K: <message>".
 //
 // -r OFFSET:LENGTH with -d writes raw bytes [OFFSET, OFFSET + LENGTH) alone, under the same output
-// name, through hc_seg_decompress_range: only the segments that hold the range are uploaded and
+// name, through the same call: only the segments that hold the range are uploaded and
 // decoded. Every FILE must then be a container; another one reports "FILE: -r needs a segmented
 // container" and counts as HC_ERR_UNSUPPORTED (65). A range outside a container is HC_ERR_ARG (71).
 #include <unistd.h>
@@ -178,16 +178,32 @@ int main(int argc, char *argv[])
         in[i].assign(std::istreambuf_iterator<char>(ifs), std::istreambuf_iterator<char>());
     });
 
-    if (compress && segmented) {  // one container per file, file after file
-        for (size_t i = 0; i < n; ++i) {
-            if (status[i]) continue;
-            const uint32_t fl = (use_diff ? HC_FLAG_DIFF : 0u) | (use_adapt ? HC_FLAG_ADAPT : 0u) |
-                                (check ? HC_SEG_CHECK_CRC32 : 0u);
+    if (compress && segmented) {  // one container per file, all files in one call
+        const uint32_t fl = (use_diff ? HC_FLAG_DIFF : 0u) | (use_adapt ? HC_FLAG_ADAPT : 0u) |
+                            (check ? HC_SEG_CHECK_CRC32 : 0u);
+        std::vector<size_t> batch;
+        for (size_t i = 0; i < n; ++i)
+            if (!status[i]) batch.push_back(i);
+        const size_t m = batch.size();
+        std::vector<const uint8_t *> ip(m);
+        std::vector<uint8_t *> op(m);
+        std::vector<uint64_t> il(m), oc(m), ol(m, 0), wd(m, width);
+        std::vector<int32_t> st(m, 0);
+        for (size_t k = 0; k < m; ++k) {
+            const size_t i = batch[k];
             out[i].resize(hc_seg_compress_bound2(in[i].size(), seg_bytes, fl, width));
-            uint64_t len = 0;
-            status[i] = hc_seg_compress2(in[i].data(), in[i].size(), fl, width, seg_bytes, out[i].data(),
-                                         out[i].size(), &len);
-            out[i].resize(status[i] ? 0 : len);
+            ip[k] = in[i].data();
+            il[k] = in[i].size();
+            op[k] = out[i].data();
+            oc[k] = out[i].size();
+        }
+        // a call-level refusal (a segment size that is no multiple of 16) is every file's status
+        const int rc = hc_seg_compress_host_batch(ip.data(), il.data(), wd.data(), (uint32_t)m, fl, seg_bytes, op.data(),
+                                                  oc.data(), ol.data(), st.data());
+        for (size_t k = 0; k < m; ++k) {
+            const size_t i = batch[k];
+            status[i] = rc ? rc : st[k];
+            out[i].resize(status[i] ? 0 : ol[k]);
         }
     } else if (compress) {  // -a: one matrix of width `width` per file
         std::vector<const uint8_t *> ip(n);
@@ -218,7 +234,7 @@ int main(int argc, char *argv[])
         // one batch (adaptive and plain streams alike), whose output sizes are unknown up
         // front: a guess, then the exact size for those that report it
         static const uint8_t kSegMagic[8] = {0x48, 0x43, 0x53, 0x45, 0x47, 0x31, 0x00, 0xFF};
-        std::vector<size_t> batch;
+        std::vector<size_t> batch, segs;
         for (size_t i = 0; i < n; ++i) {
             if (status[i]) continue;
             if (in[i].size() < 8 || !std::equal(kSegMagic, kSegMagic + 8, in[i].begin())) {
@@ -226,19 +242,47 @@ int main(int argc, char *argv[])
                 else batch.push_back(i);
                 continue;
             }
-            if (ranged) {
-                out[i].resize(std::min<uint64_t>(r_length, 520 * (uint64_t)in[i].size()));  // (no container decodes to more)
-                uint64_t len = 0;
-                status[i] = hc_seg_decompress_range(in[i].data(), in[i].size(), r_offset, r_length, out[i].data(),
-                                                    out[i].size(), &len, &bad_seg[i]);
-                out[i].resize(status[i] ? 0 : len);
-                continue;
+            segs.push_back(i);  // a segmented container
+        }
+        // all containers in one call, each whole or at the range. A whole output is sized like a plain
+        // stream's: a guess first, the header's raw_len only for a container whose header and index
+        // passed and that reports the guess too small
+        for (int pass = 0; pass < 2 && !segs.empty(); ++pass) {
+            const size_t m = segs.size();
+            std::vector<const uint8_t *> ip(m);
+            std::vector<uint8_t *> op(m);
+            // (-r 0:2^64-1 is a range outside every container, not the batch call's "whole" item: one
+            // byte less is as far outside)
+            const uint64_t len = r_length == HC_SEG_WHOLE ? r_length - 1 : r_length;
+            std::vector<uint64_t> il(m), oc(m), ol(m, 0), bs(m, UINT64_MAX), ro(m, r_offset), rl(m, len);
+            std::vector<int32_t> st(m, 0);
+            for (size_t k = 0; k < m; ++k) {
+                const size_t i = segs[k];
+                hc_seg_info_t info;
+                il[k] = in[i].size();
+                if (ranged) out[i].resize(std::min<uint64_t>(r_length, 520 * il[k]));  // (no container decodes to more)
+                else if (pass == 0 && hc_seg_info(in[i].data(), il[k], &info) == HC_OK)
+                    out[i].resize(std::min<uint64_t>(info.raw_len, std::max<uint64_t>(il[k] * 8, 65536)));
+                ip[k] = in[i].data();
+                op[k] = out[i].data();
+                oc[k] = out[i].size();
             }
-            uint8_t *p = nullptr;  // a segmented container
-            uint64_t len = 0;
-            status[i] = hc_seg_decompress_alloc(in[i].data(), in[i].size(), &p, &len, &bad_seg[i]);
-            if (!status[i]) out[i].assign(p, p + len);
-            hc_free(p);
+            const int rc = hc_seg_decompress_host_batch(ip.data(), il.data(), ranged ? ro.data() : nullptr,
+                                                        ranged ? rl.data() : nullptr, (uint32_t)m, op.data(), oc.data(),
+                                                        ol.data(), st.data(), bs.data());
+            std::vector<size_t> again;
+            for (size_t k = 0; k < m; ++k) {
+                const size_t i = segs[k];
+                if (!rc && !ranged && st[k] == HC_ERR_CAPACITY && pass == 0) {
+                    out[i].resize(ol[k]);
+                    again.push_back(i);
+                    continue;
+                }
+                status[i] = rc ? rc : st[k];
+                if (!rc) bad_seg[i] = bs[k];
+                out[i].resize(status[i] ? 0 : ol[k]);
+            }
+            segs.swap(again);
         }
         for (int pass = 0; pass < 2 && !batch.empty(); ++pass) {
             const size_t m = batch.size();

@@ -22,6 +22,10 @@
 //           for the covered segments only; one that the range covers in part, or any at an offset
 //           that is no multiple of 4, decodes into a slot of the workspace, and a pack launch
 //           (hc_pipe.hip) moves its covered part to its place in out before seg_close
+//   batch   many inputs, or many (container, range) pairs, per call (hc_seg_*_batch_dev): the
+//           segments of all items in one concatenated array, so the same coder launches serve
+//           them all; the glue kernels per item (the *_batch_kernel forms further down), the item
+//           records carried to the device as kernel arguments by seg_items_kernel
 //
 // Every launch is asynchronous on the caller's stream; no allocation, no host synchronisation,
 // no host read of device memory in the device entry points. A container-level error zeroes
@@ -639,6 +643,596 @@ int decode_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, ui
     return HC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Batches (hc_seg_*_batch_dev): many items per call over one concatenated segment array, so one
+// launch of each coder serves them all. The glue kernels above, per item: the item records reach
+// the device as kernel arguments, a chunk per launch (seg_items_kernel; the only launches that
+// grow with n_items), and live in the workspace from then on. Seal, open and close run one
+// workgroup per item, each with its own tiled scan; plan and gather run over the segments and
+// find their item by search and by the map that plan leaves. ctl is one word per item.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kEncChunk = 32, kDecChunk = 16;  // items per descriptor launch (arguments: 4 KB at most)
+
+struct EncItem {
+    uint64_t seg0, n;  // its segments: [seg0, seg0 + n) of the arrays; n 0: hs alone
+    uint64_t full, last, slot_full, cap_full, cap_last, width;
+    uint64_t in_off, slot_off, out_off, out_cap;  // from in, the slots, out
+    uint64_t raw_len;
+    int64_t hs;  // the host-decided status
+};
+struct DecItem {
+    uint64_t in_off, in_len, skip;
+    uint64_t flags, raw_len, seg_bytes, width;  // header words 1 .. 4 (0: the magic, 5: n)
+    uint64_t n, full, last, offset, length, out_cap;
+    uint64_t k0, count, nslots, slot;
+    uint64_t out_off, slot_off;  // from out, the slots
+    uint64_t seg0, slot0;        // its first entry of the segment arrays, of the copy arrays
+    uint32_t check;
+    int32_t hs;  // the host-decided status
+};
+static_assert(sizeof(EncItem) == 112 && sizeof(DecItem) == 176, "the work bounds of hcodec.h count these");
+
+template <class Item, uint32_t N>
+struct ItemChunk {
+    Item it[N];
+    Item *dst;
+    uint32_t count;
+};
+static_assert(sizeof(ItemChunk<EncItem, kEncChunk>) <= 3968 && sizeof(ItemChunk<DecItem, kDecChunk>) <= 3968,
+              "kernel arguments");
+
+template <class Chunk>
+__global__ __launch_bounds__(64) void seg_items_kernel(Chunk c)
+{
+    if (threadIdx.x < c.count) c.dst[threadIdx.x] = c.it[threadIdx.x];
+}
+
+// collects the records of a call and launches a chunk whenever one is full
+template <class Item, uint32_t N>
+struct ItemFeed {
+    ItemChunk<Item, N> c;
+    Item *dst;
+    hipStream_t st;
+    ItemFeed(Item *d, hipStream_t s) : dst(d), st(s) { c.count = 0; }
+    void flush()
+    {
+        if (c.count == 0) return;
+        c.dst = dst;
+        seg_items_kernel<<<1, 64, 0, st>>>(c);
+        dst += c.count;
+        c.count = 0;
+    }
+    void push(const Item &it)
+    {
+        c.it[c.count++] = it;
+        if (c.count == N) flush();
+    }
+};
+
+struct EncBatchWs {
+    EncWs s;  // the single call's arrays over all N segments (its ctl word is not used)
+    EncItem *items;
+    uint32_t *seg_item;  // segment -> item
+    uint64_t *ctl;       // [i] 1: item i is sealed, the gather may copy
+    uint64_t total;
+};
+EncBatchWs carve_enc_batch(void *work, uint64_t n_items, uint64_t n, uint64_t slot_bytes, uint64_t awork_bytes,
+                           bool check)
+{
+    EncBatchWs w;
+    w.s = carve_enc(work, n, slot_bytes, awork_bytes, check);
+    uint8_t *p = static_cast<uint8_t *>(work);
+    uint64_t o = w.s.total;
+    auto take = [&](uint64_t bytes) {
+        uint8_t *q = p ? p + o : nullptr;
+        o += align16(bytes);
+        return q;
+    };
+    w.items = reinterpret_cast<EncItem *>(take(sizeof(EncItem) * n_items));
+    w.seg_item = reinterpret_cast<uint32_t *>(take(4 * n));
+    w.ctl = reinterpret_cast<uint64_t *>(take(8 * n_items));
+    w.total = o;
+    return w;
+}
+
+struct PlanBatchArgs {
+    const EncItem *items;
+    uint32_t n_items;
+    uint64_t n;
+    uint64_t *in_offs, *in_lens, *widths, *out_offs, *out_caps, *out_lens;
+    int32_t *status;
+    uint32_t *seg_item;
+};
+
+// seg_plan_kernel over the concatenated segments: segment k belongs to the last item whose seg0
+// is <= k (an item without segments shares its seg0 with the next one, which the search passes)
+__global__ __launch_bounds__(256) void seg_plan_batch_kernel(PlanBatchArgs a)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= a.n) return;
+    uint32_t lo = 0, hi = a.n_items;  // items[lo].seg0 <= k < items[hi].seg0 (hi == n_items: the end)
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.items[mid].seg0 <= k) lo = mid;
+        else hi = mid;
+    }
+    const EncItem &it = a.items[lo];
+    const uint64_t j = k - it.seg0;
+    const bool tail = j == it.n - 1;
+    a.in_offs[k] = it.in_off + j * it.full;
+    a.in_lens[k] = tail ? it.last : it.full;
+    a.widths[k] = it.width;
+    a.out_offs[k] = it.slot_off + j * it.slot_full;
+    a.out_caps[k] = tail ? it.cap_last : it.cap_full;
+    a.out_lens[k] = 0;
+    a.status[k] = HC_ERR_DEVICE;  // every segment is coded by exactly one launch, which overwrites this
+    a.seg_item[k] = lo;
+}
+
+struct SealBatchArgs {
+    const EncItem *items;
+    const uint64_t *enc_lens;
+    const int32_t *seg_status;
+    const uint32_t *crc;  // null: unchecked containers
+    uint64_t *dst_offs, *ctl;
+    uint8_t *out;
+    uint64_t *out_lens;
+    int32_t *status;
+    uint64_t magic, flags, seg_bytes;  // header words 0, 1 and 3
+};
+
+// seg_seal_kernel for item blockIdx.x: its segments' places from out (dst_offs), its verdict, its
+// header and index at out + out_off
+__global__ __launch_bounds__(kScan) void seg_seal_batch_kernel(SealBatchArgs a)
+{
+    __shared__ uint64_t part[kScan / 64];
+    __shared__ unsigned long long s_bad, s_end;
+    const uint32_t tid = threadIdx.x, item = blockIdx.x;
+    const EncItem it = a.items[item];
+    if (it.hs != 0) {  // decided on the host: no segment, no output byte
+        if (tid == 0) {
+            a.status[item] = (int32_t)it.hs;
+            a.out_lens[item] = 0;
+            a.ctl[item] = 0;
+        }
+        return;
+    }
+    if (tid == 0) {
+        s_bad = kNoSeg;
+        s_end = 0;
+    }
+    __syncthreads();
+    const uint64_t *enc_lens = a.enc_lens + it.seg0;
+    const int32_t *seg_status = a.seg_status + it.seg0;
+    const uint32_t *crc = a.crc ? a.crc + it.seg0 : nullptr;
+    const uint64_t idx_end = index_end(it.n, crc != nullptr);
+    uint64_t carry = align16(idx_end);  // where segment 0 starts
+    uint64_t bad = kNoSeg;
+    for (uint64_t base = 0; base < it.n; base += kScan) {
+        const uint64_t k = base + tid;
+        const bool in = k < it.n;
+        const uint64_t len = in ? enc_lens[k] : 0;
+        if (in && seg_status[k] != 0 && bad == kNoSeg) bad = k;
+        uint64_t total;
+        const uint64_t off = sat_add(carry, block_scan(in ? align16(len) : 0, part, total));
+        if (in) a.dst_offs[it.seg0 + k] = it.out_off + off;  // (read by the gather of a sealed item alone)
+        if (in && k == it.n - 1) s_end = sat_add(off, len);  // no padding after the last segment
+        carry = sat_add(carry, total);
+    }
+    if (bad != kNoSeg) atomicMin(&s_bad, (unsigned long long)bad);
+    __syncthreads();
+    const uint64_t first_bad = s_bad, end = s_end;
+    int32_t st = 0;
+    if (first_bad != kNoSeg) st = seg_status[first_bad];
+    else if (end > it.out_cap) st = HC_ERR_CAPACITY;
+    if (tid == 0) {
+        a.status[item] = st;
+        a.out_lens[item] = (st == 0 || st == HC_ERR_CAPACITY) ? end : 0;
+        a.ctl[item] = st == 0 ? 1 : 0;
+    }
+    if (st != 0) return;
+    // sealed: end <= out_cap, so the header, the index and its padding lie inside the item's output
+    uint64_t *o64 = reinterpret_cast<uint64_t *>(a.out + it.out_off);
+    uint32_t *o32 = reinterpret_cast<uint32_t *>(a.out + it.out_off);
+    if (tid < 6)
+        o64[tid] = tid == 0 ? a.magic : tid == 1 ? a.flags : tid == 2 ? it.raw_len : tid == 3 ? a.seg_bytes
+                   : tid == 4 ? it.width : it.n;
+    if (tid >= 8 && tid < 8 + (align16(idx_end) - idx_end) / 4) o32[idx_end / 4 + (tid - 8)] = 0;
+    for (uint64_t k = tid; k < it.n; k += kScan) o64[6 + k] = enc_lens[k];
+    if (crc)
+        for (uint64_t k = tid; k < it.n; k += kScan) o32[12 + 2 * it.n + k] = crc[k];
+}
+
+// seg_gather_kernel over the concatenated segments: dst_offs count from out, and a segment is its
+// item's last one when it ends the item's run
+__global__ __launch_bounds__(256) void seg_gather_batch_kernel(const uint8_t *slots, const uint64_t *slot_offs,
+                                                               const uint64_t *enc_lens, const uint64_t *dst_offs,
+                                                               const uint64_t *ctl, const uint32_t *seg_item,
+                                                               const EncItem *items, uint64_t n, uint8_t *out)
+{
+    for (uint64_t k = blockIdx.x; k < n; k += gridDim.x) {
+        const uint32_t item = seg_item[k];
+        if (ctl[item] == 0) continue;  // not sealed: nothing is copied
+        const bool last = k == items[item].seg0 + items[item].n - 1;
+        const uint64_t len = enc_lens[k];
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(slots + slot_offs[k]);
+        u32x4 *dst = reinterpret_cast<u32x4 *>(out + dst_offs[k]);
+        const uint64_t chunks = len / 16;
+        for (uint64_t c = threadIdx.x; c < chunks; c += 256) dst[c] = src[c];
+        const uint32_t rem = (uint32_t)(len & 15u);
+        if (rem == 0 || threadIdx.x != 255) continue;
+        if (last) {
+            const uint8_t *s8 = reinterpret_cast<const uint8_t *>(src + chunks);
+            uint8_t *d8 = reinterpret_cast<uint8_t *>(dst + chunks);
+            for (uint32_t b = 0; b < rem; ++b) d8[b] = s8[b];
+        } else {
+            u32x4 v = src[chunks];  // inside the slot: slots are multiples of 16 bytes
+            uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (uint32_t d = 0; d < 4; ++d) {
+                if (rem <= 4 * d) w[d] = 0;
+                else if (rem < 4 * d + 4) w[d] &= (1u << (8 * (rem - 4 * d))) - 1u;
+            }
+            v.x = w[0];
+            v.y = w[1];
+            v.z = w[2];
+            v.w = w[3];
+            dst[chunks] = v;
+        }
+    }
+}
+
+// the sums an encode batch is sized by, over the items that pass host_status; false: too many segments
+struct EncTotals {
+    uint64_t n, slot_bytes, in_bytes;
+};
+bool enc_totals(const hc_seg_enc_item_t *items, uint32_t n_items, int use_adapt, uint64_t seg_bytes, EncTotals &t)
+{
+    t = EncTotals{0, 0, 0};
+    for (uint32_t i = 0; i < n_items; ++i) {
+        if (host_status(items[i].in_len, use_adapt, items[i].width)) continue;
+        EncPlan p;
+        if (!enc_plan(items[i].in_len, seg_bytes, use_adapt, items[i].width, p)) return false;
+        t.n += p.c.n;
+        t.slot_bytes += p.slot_bytes;
+        t.in_bytes += items[i].in_len;
+        if (t.n > kMaxSegs) return false;
+    }
+    return true;
+}
+EncBatchWs enc_batch_ws(void *work, uint32_t n_items, const EncTotals &t, int use_adapt, bool check)
+{
+    const uint64_t aw = (use_adapt && t.n) ? hc::adapt_encode_work_bound(t.in_bytes, (uint32_t)t.n) : 0;
+    return carve_enc_batch(work, n_items, t.n, t.slot_bytes, aw, check);
+}
+
+// --- decode ---
+struct DecBatchWs {
+    uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;
+    int32_t *status;
+    uint32_t *crc;  // entry k of a checked item's segment k alone is written and read
+    uint64_t *ctl;  // [i] item i's container-level status (0, HC_ERR_SEG_HEADER, HC_ERR_CAPACITY, or hs)
+    DecItem *items;
+    uint64_t *cp_src, *cp_len, *cp_dst;
+    uint8_t *slots;
+    void *awork;
+    uint64_t awork_bytes, total;
+};
+DecBatchWs carve_dec_batch(void *work, uint64_t n_items, uint64_t count, uint64_t nslots, uint64_t slot_bytes,
+                           uint64_t awork_bytes)
+{
+    DecBatchWs w;
+    uint8_t *p = static_cast<uint8_t *>(work);
+    uint64_t o = 0;
+    auto take = [&](uint64_t bytes) {
+        uint8_t *q = p ? p + o : nullptr;  // null: sizing only
+        o += align16(bytes);
+        return q;
+    };
+    w.in_offs = reinterpret_cast<uint64_t *>(take(8 * count));
+    w.in_lens = reinterpret_cast<uint64_t *>(take(8 * count));
+    w.out_offs = reinterpret_cast<uint64_t *>(take(8 * count));
+    w.out_caps = reinterpret_cast<uint64_t *>(take(8 * count));
+    w.out_lens = reinterpret_cast<uint64_t *>(take(8 * count));
+    w.status = reinterpret_cast<int32_t *>(take(4 * count));
+    w.crc = reinterpret_cast<uint32_t *>(take(4 * count));
+    w.ctl = reinterpret_cast<uint64_t *>(take(8 * n_items));
+    w.items = reinterpret_cast<DecItem *>(take(sizeof(DecItem) * n_items));
+    w.cp_src = reinterpret_cast<uint64_t *>(take(8 * nslots));
+    w.cp_len = reinterpret_cast<uint64_t *>(take(8 * nslots));
+    w.cp_dst = reinterpret_cast<uint64_t *>(take(8 * nslots));
+    w.slots = take(slot_bytes);
+    w.awork = take(awork_bytes);
+    w.awork_bytes = awork_bytes;
+    w.total = o;
+    return w;
+}
+
+struct OpenBatchArgs {
+    const uint8_t *in;
+    const DecItem *items;
+    uint64_t magic;          // header word 0
+    uint64_t out_d, slot_d;  // out and the slots from the batch's output base
+    uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;
+    uint64_t *cp_src, *cp_len, *cp_dst;
+    int32_t *status;
+    uint64_t *ctl;
+};
+
+// seg_open_kernel for item blockIdx.x: its header and index, its covered segments' entries from
+// seg0 on (input offsets from the call's `in`, outputs from the call's base), its copies from slot0
+// on (sources from the slots' start, destinations from `out`)
+__global__ __launch_bounds__(kScan) void seg_open_batch_kernel(OpenBatchArgs a)
+{
+    __shared__ uint64_t part[kScan / 64];
+    __shared__ uint32_t s_err;
+    const uint32_t tid = threadIdx.x, item = blockIdx.x;
+    const DecItem it = a.items[item];
+    if (it.hs != 0) {  // decided on the host: no segment (count and nslots are 0), no output byte
+        if (tid == 0) a.ctl[item] = (uint64_t)it.hs;
+        return;
+    }
+    uint64_t *cp_src = a.cp_src + it.slot0, *cp_len = a.cp_len + it.slot0, *cp_dst = a.cp_dst + it.slot0;
+    if (tid == 0) s_err = 0;
+    for (uint64_t s = tid; s < it.nslots; s += kScan) cp_len[s] = 0;  // a slot nothing is staged in
+    __syncthreads();
+    bool err = false;
+    const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in + it.in_off);
+    if (tid < 6) {
+        const uint64_t want = tid == 0 ? a.magic : tid == 1 ? it.flags : tid == 2 ? it.raw_len
+                              : tid == 3 ? it.seg_bytes : tid == 4 ? it.width : it.n;
+        if (i64[tid] != want) err = true;
+    }
+    const uint64_t end = it.offset + it.length;  // (inside raw_len: the host's check)
+    const bool all_staged = (it.offset & 3u) != 0;
+    const uint64_t tail_slot = it.offset != it.k0 * it.full;  // aligned: after segment k0's slot, if it has one
+    uint64_t carry = align16(index_end(it.n, it.check != 0));
+    for (uint64_t base = 0; base < it.n; base += kScan) {
+        const uint64_t k = base + tid;
+        const bool in = k < it.n;
+        const uint64_t len = in ? i64[6 + k] : 0;
+        const bool big = len > it.in_len;
+        uint64_t total;
+        const uint64_t off = sat_add(carry, block_scan(in && !big ? align16(len) : 0, part, total));
+        if (in) {
+            const bool tail = k == it.n - 1;
+            if (big || off > it.in_len || len > it.in_len - off) err = true;
+            else if (tail && off + len != it.in_len) err = true;  // truncated, or trailing bytes
+        }
+        if (in && k >= it.k0 && k - it.k0 < it.count) {
+            const uint64_t i = k - it.k0, e_i = it.seg0 + i;
+            const uint64_t b = k * it.full, cap = k == it.n - 1 ? it.last : it.full, e = b + cap;
+            const uint64_t lo = b > it.offset ? b : it.offset, hi = e < end ? e : end;
+            a.in_offs[e_i] = it.in_off + off - it.skip;  // (a wrapped value is never read: err zeroes in_lens)
+            a.in_lens[e_i] = len;
+            a.out_caps[e_i] = cap;
+            a.out_lens[e_i] = 0;
+            a.status[e_i] = HC_ERR_DEVICE;  // overwritten by the launch that owns the segment
+            if (all_staged || lo != b || hi != e) {
+                const uint64_t s = all_staged ? i : (i == 0 ? 0 : tail_slot);
+                a.out_offs[e_i] = a.slot_d + it.slot_off + s * it.slot;
+                cp_src[s] = it.slot_off + s * it.slot + (lo - b);
+                cp_len[s] = hi - lo;
+                cp_dst[s] = it.out_off + (lo - it.offset);
+            } else {
+                a.out_offs[e_i] = a.out_d + it.out_off + (b - it.offset);
+            }
+        }
+        carry = sat_add(carry, total);
+    }
+    if (err) s_err = 1;
+    __syncthreads();
+    const int32_t st = s_err ? HC_ERR_SEG_HEADER : (it.length > it.out_cap ? HC_ERR_CAPACITY : 0);
+    if (tid == 0) a.ctl[item] = (uint64_t)st;
+    if (st == 0) return;
+    // nothing of this item may be decoded or copied: empty inputs, which the coders answer with
+    // HC_ERR_HEADER before they touch anything (and which the CRC gate then passes over), empty copies
+    for (uint64_t i = tid; i < it.count; i += kScan) a.in_lens[it.seg0 + i] = 0;
+    for (uint64_t s = tid; s < it.nslots; s += kScan) cp_len[s] = 0;
+}
+
+struct CloseBatchArgs {
+    const uint8_t *in;
+    const DecItem *items;
+    const uint64_t *seg_out_lens, *seg_out_caps, *ctl;
+    const int32_t *seg_status;
+    const uint32_t *crc;
+    uint64_t *out_lens, *bad_segments;
+    int32_t *status;
+};
+
+// seg_close_kernel for item blockIdx.x
+__global__ __launch_bounds__(kScan) void seg_close_batch_kernel(CloseBatchArgs a)
+{
+    __shared__ unsigned long long s_bad;
+    const uint32_t tid = threadIdx.x, item = blockIdx.x;
+    const DecItem &it = a.items[item];
+    const uint64_t seg0 = it.seg0, count = it.count, k0 = it.k0, length = it.length;
+    const uint64_t *out_lens = a.seg_out_lens + seg0, *out_caps = a.seg_out_caps + seg0;
+    const int32_t *seg_status = a.seg_status + seg0;
+    // checked containers: the decoded bytes' crc, and the index's from k0
+    const uint32_t *crc = it.check ? a.crc + seg0 : nullptr;
+    const uint32_t *want_crc = reinterpret_cast<const uint32_t *>(a.in + it.in_off + 48 + 8 * it.n) + k0;
+    if (tid == 0) s_bad = kNoSeg;
+    __syncthreads();
+    const int32_t top = (int32_t)a.ctl[item];
+    if (top == 0) {
+        uint64_t bad = kNoSeg;
+        for (uint64_t i = tid; i < count && bad == kNoSeg; i += kScan)
+            if (seg_status[i] != 0 || out_lens[i] != out_caps[i] || (crc && crc[i] != want_crc[i])) bad = i;
+        if (bad != kNoSeg) atomicMin(&s_bad, (unsigned long long)bad);
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const uint64_t bad = s_bad;
+    int32_t st = top;
+    uint64_t len = top == HC_ERR_CAPACITY ? length : 0;
+    if (top == 0) {
+        if (bad != kNoSeg) {
+            st = seg_status[bad];
+            // 64: it wanted more room than its cut; 0: it decoded to fewer bytes, or to the wrong ones
+            if (st == 0 && out_lens[bad] == out_caps[bad]) st = HC_ERR_SEG_CHECK;
+            else if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
+        } else {
+            len = length;
+        }
+    }
+    a.status[item] = st;
+    a.out_lens[item] = len;
+    if (a.bad_segments) a.bad_segments[item] = bad == kNoSeg ? kNoSeg : k0 + bad;
+}
+
+// One decoder item on the host: its status when the host decides it (0: none), else its cuts, its
+// range (whole: (0, raw_len)) and its sizes. The segment arrays hold the items in four groups, so
+// that each launch covers one run of entries: plain unchecked, plain checked, adaptive checked,
+// adaptive unchecked (FGK the first two, adaptive the last two, CRC the middle two).
+struct DecOne {
+    int hs;
+    Cuts c;
+    uint64_t offset, length;
+    DecPlan p;
+    uint32_t group;
+    bool adapt, check;
+};
+DecOne dec_one(const hc_seg_dec_item_t &it)
+{
+    DecOne d;
+    d.hs = 0;
+    d.c = Cuts{0, 0, 0};
+    d.offset = d.length = 0;
+    d.p.cv = Cover{0, 0};
+    d.p.nslots = d.p.slot = d.p.raw = 0;
+    d.group = 0;
+    d.adapt = d.check = false;
+    if (!info_ok(it.info, it.in_len, d.c)) {
+        d.hs = HC_ERR_SEG_HEADER;
+        return d;
+    }
+    const bool whole = it.length == HC_SEG_WHOLE && it.offset == 0;
+    d.offset = it.offset;
+    d.length = whole ? it.info.raw_len : it.length;
+    if (!whole && !range_ok(it.info.raw_len, it.offset, it.length)) {
+        d.hs = HC_ERR_ARG;
+        return d;
+    }
+    d.adapt = (it.info.flags & HC_FLAG_ADAPT) != 0;
+    d.check = checked(it.info.flags);
+    d.group = d.adapt ? (d.check ? 2u : 3u) : (d.check ? 1u : 0u);
+    d.p = dec_plan(d.c, d.offset, d.length, whole);
+    return d;
+}
+
+struct DecTotals {
+    uint64_t seg[4];  // covered segments per group
+    uint64_t count, nslots, slot_bytes;
+    uint64_t a_enc, a_raw, a_count;  // the adaptive items: encoded bytes (a bound), raw bytes, segments
+};
+// enc_totals: per item, a bound of its covered segments' encoded bytes (null: in_len)
+bool dec_totals(const hc_seg_dec_item_t *items, uint32_t n_items, const uint64_t *enc_totals, DecTotals &t)
+{
+    memset(&t, 0, sizeof(t));
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const DecOne d = dec_one(items[i]);
+        if (d.hs) continue;
+        if (d.c.n > kMaxSegs) return false;
+        t.seg[d.group] += d.p.cv.count;
+        t.count += d.p.cv.count;
+        t.nslots += d.p.nslots;
+        t.slot_bytes += d.p.nslots * d.p.slot;
+        if (d.adapt && d.p.cv.count) {
+            t.a_enc += enc_totals ? enc_totals[i] : items[i].in_len;
+            t.a_raw += d.p.raw;
+            t.a_count += d.p.cv.count;
+        }
+        if (t.count > kMaxSegs) return false;
+    }
+    return true;
+}
+DecBatchWs dec_batch_ws(void *work, uint32_t n_items, const DecTotals &t)
+{
+    const uint64_t aw = t.a_count ? hc::adapt_decode_work_bound(t.a_enc, t.a_raw, (uint32_t)t.a_count) : 0;
+    return carve_dec_batch(work, n_items, t.count, t.nslots, t.slot_bytes, aw);
+}
+
+// hc_seg_decompress_batch_dev; the host batch call passes its compact uploads' skips and spans
+int decode_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_dec_item_t *items, uint32_t n_items,
+                     uint64_t *out_lens, int32_t *status, uint64_t *bad_segments, void *work, uint64_t work_bytes,
+                     void *stream, const uint64_t *skips, const uint64_t *enc_totals)
+{
+    if (n_items == 0) return HC_OK;
+    if (!in || !out || !items || !out_lens || !status || !work) return HC_ERR_ARG;
+    if (!aligned16(in) || !aligned16(out) || !aligned16(work)) return HC_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if ((items[i].in_off | items[i].out_off) & 15u) return HC_ERR_ARG;
+    DecTotals t;
+    if (!dec_totals(items, n_items, enc_totals, t)) return HC_ERR_ARG;
+    const DecBatchWs w = dec_batch_ws(work, n_items, t);
+    if (work_bytes < w.total) return HC_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+
+    // the groups' first entries, and the records
+    uint64_t next[4] = {0, t.seg[0], t.seg[0] + t.seg[1], t.seg[0] + t.seg[1] + t.seg[2]};
+    const uint64_t n_fgk = next[2], crc0 = next[1], n_crc = t.seg[1] + t.seg[2];
+    uint64_t slot0 = 0, slot_off = 0;
+    ItemFeed<DecItem, kDecChunk> feed(w.items, st);
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const hc_seg_dec_item_t &h = items[i];
+        const DecOne d = dec_one(h);
+        DecItem r;
+        memset(&r, 0, sizeof(r));
+        r.hs = d.hs;
+        if (!d.hs) {
+            r = DecItem{h.in_off, h.in_len, skips ? skips[i] : 0,
+                        h.info.flags & 0xFFFFu, h.info.raw_len, h.info.seg_bytes, h.info.width,
+                        d.c.n, d.c.full, d.c.last, d.offset, d.length, h.out_cap,
+                        d.p.cv.k0, d.p.cv.count, d.p.nslots, d.p.slot,
+                        h.out_off, slot_off, next[d.group], slot0, d.check ? 1u : 0u, 0};
+            next[d.group] += d.p.cv.count;
+            slot0 += d.p.nslots;
+            slot_off += d.p.nslots * d.p.slot;
+        }
+        feed.push(r);
+    }
+    feed.flush();
+    HC_CK(hipGetLastError());
+
+    // one output base for the call: whichever of out and the slots lies lower
+    uint8_t *base = (t.nslots && w.slots < out) ? w.slots : out;
+    const OpenBatchArgs oa{in, w.items, get64(kMagic), (uint64_t)(out - base), t.nslots ? (uint64_t)(w.slots - base) : 0,
+                           w.in_offs, w.in_lens, w.out_offs, w.out_caps, w.out_lens,
+                           w.cp_src, w.cp_len, w.cp_dst, w.status, w.ctl};
+    seg_open_batch_kernel<<<n_items, kScan, 0, st>>>(oa);
+    HC_CK(hipGetLastError());
+    if (n_fgk) {
+        Batch b{in, w.in_offs, w.in_lens, (uint32_t)n_fgk, base, w.out_offs, w.out_caps, w.out_lens, w.status, 0};
+        HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
+    }
+    if (t.count > n_fgk) {
+        Batch b{in, w.in_offs + n_fgk, w.in_lens + n_fgk, (uint32_t)(t.count - n_fgk), base, w.out_offs + n_fgk,
+                w.out_caps + n_fgk, w.out_lens + n_fgk, w.status + n_fgk, 0};
+        HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
+    }
+    // the checked items' segments that decoded cleanly to their cut's length; an item whose verdict
+    // is set has empty inputs, which no coder answers with status 0, so the per-segment gate alone
+    // keeps the launch away from it
+    if (n_crc)
+        HC_CK(hc::launch_crc32(base, w.out_offs + crc0, w.out_caps + crc0, n_crc, w.crc + crc0,
+                               hc::CrcGate{nullptr, w.status + crc0, w.out_lens + crc0}, st));
+    if (t.nslots) HC_CK(hc::launch_pack(w.slots, w.cp_src, w.cp_len, (uint32_t)t.nslots, out, w.cp_dst, st));
+    const CloseBatchArgs ca{in, w.items, w.out_lens, w.out_caps, w.ctl, w.status, w.crc, out_lens, bad_segments, status};
+    seg_close_batch_kernel<<<n_items, kScan, 0, st>>>(ca);
+    HC_CK(hipGetLastError());
+    return HC_OK;
+}
+
+// the host batch calls' sub-batch limit, as hc_pipe.hip reads it
+uint64_t pipe_bytes()
+{
+    const char *v = getenv("HC_PIPE_BYTES");
+    const uint64_t x = (v && *v) ? strtoull(v, nullptr, 0) : 0;
+    return x ? x : 1ull << 30;
+}
+
 }  // namespace
 
 extern "C" {
@@ -848,6 +1442,292 @@ int hc_seg_decompress_range(const uint8_t *in, uint64_t in_len, uint64_t offset,
     if (bad_segment) *bad_segment = h[2];
     if (status) return status;
     if (h[0]) HC_CK(hipMemcpy(out, dout.p, h[0], hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+uint64_t hc_seg_compress_batch_work_bound(const hc_seg_enc_item_t *items, uint32_t n_items, uint32_t flags,
+                                          uint64_t seg_bytes)
+{
+    if ((flags & ~kSegFlags) || (seg_bytes & 15u) || (!items && n_items)) return 0;
+    const int use_adapt = (flags & HC_FLAG_ADAPT) ? 1 : 0;
+    EncTotals t;
+    if (!enc_totals(items, n_items, use_adapt, seg_bytes ? seg_bytes : HC_SEG_DEFAULT_BYTES, t)) return 0;
+    return enc_batch_ws(nullptr, n_items, t, use_adapt, checked(flags)).total;
+}
+
+int hc_seg_compress_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_enc_item_t *items, uint32_t n_items,
+                              uint32_t flags, uint64_t seg_bytes, uint64_t *out_lens, int32_t *status, void *work,
+                              uint64_t work_bytes, void *stream)
+{
+    if (n_items == 0) return HC_OK;
+    if (!out || !items || !out_lens || !status || !work) return HC_ERR_ARG;
+    if (flags & ~kSegFlags) return HC_ERR_ARG;
+    if (seg_bytes & 15u) return HC_ERR_ARG;
+    if (!aligned16(in) || !aligned16(out) || !aligned16(work)) return HC_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        if (!in && items[i].in_len) return HC_ERR_ARG;
+        if ((items[i].in_off | items[i].out_off) & 15u) return HC_ERR_ARG;
+    }
+    const int use_adapt = (flags & HC_FLAG_ADAPT) ? 1 : 0;
+    if (!seg_bytes) seg_bytes = HC_SEG_DEFAULT_BYTES;
+    const bool check = checked(flags);
+    EncTotals t;
+    if (!enc_totals(items, n_items, use_adapt, seg_bytes, t)) return HC_ERR_ARG;
+    const EncBatchWs w = enc_batch_ws(work, n_items, t, use_adapt, check);
+    if (work_bytes < w.total) return HC_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint32_t n = (uint32_t)t.n;
+
+    uint64_t seg0 = 0, slot_off = 0;
+    ItemFeed<EncItem, kEncChunk> feed(w.items, st);
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const hc_seg_enc_item_t &h = items[i];
+        EncItem r;
+        memset(&r, 0, sizeof(r));
+        r.seg0 = seg0;
+        r.hs = host_status(h.in_len, use_adapt, h.width);
+        if (!r.hs) {
+            EncPlan p;
+            (void)enc_plan(h.in_len, seg_bytes, use_adapt, h.width, p);
+            r = EncItem{seg0, p.c.n, p.c.full, p.c.last, p.slot_full, p.cap_full, p.cap_last,
+                        use_adapt ? h.width : 0, h.in_off, slot_off, h.out_off, h.out_cap, h.in_len, 0};
+            seg0 += p.c.n;
+            slot_off += p.slot_bytes;
+        }
+        feed.push(r);
+    }
+    feed.flush();
+    HC_CK(hipGetLastError());
+    const EncWs &s = w.s;
+    if (n) {
+        const PlanBatchArgs pa{w.items, n_items, t.n, s.in_offs, s.in_lens, s.widths, s.out_offs, s.out_caps,
+                               s.out_lens, s.status, w.seg_item};
+        seg_plan_batch_kernel<<<(n + 255) / 256, 256, 0, st>>>(pa);
+        HC_CK(hipGetLastError());
+        Batch b{in ? in : out, s.in_offs, s.in_lens, n, s.slots, s.out_offs, s.out_caps, s.out_lens, s.status,
+                flags & HC_FLAG_DIFF};
+        // the raw bytes of every cut, before the diff model (an empty input has one empty segment: crc 0)
+        if (check) HC_CK(hc::launch_crc32(b.in, s.in_offs, s.in_lens, n, s.crc, hc::CrcGate{nullptr, nullptr, nullptr}, st));
+        if (use_adapt) HC_CK(hc::adapt_encode_batch(b, s.widths, s.awork, s.awork_bytes, st));
+        else HC_CK(hc::launch_encode(b, (flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
+    }
+    const SealBatchArgs sa{w.items, s.out_lens, s.status, check ? s.crc : nullptr, s.dst_offs, w.ctl, out, out_lens,
+                           status, get64(kMagic), flags & 0xFFFFu, seg_bytes};
+    seg_seal_batch_kernel<<<n_items, kScan, 0, st>>>(sa);
+    if (n)
+        seg_gather_batch_kernel<<<n < 65536u ? n : 65536u, 256, 0, st>>>(s.slots, s.out_offs, s.out_lens, s.dst_offs,
+                                                                         w.ctl, w.seg_item, w.items, t.n, out);
+    HC_CK(hipGetLastError());
+    return HC_OK;
+}
+
+uint64_t hc_seg_decompress_batch_work_bound(const hc_seg_dec_item_t *items, uint32_t n_items)
+{
+    if (!items && n_items) return 0;
+    DecTotals t;
+    if (!dec_totals(items, n_items, nullptr, t)) return 0;
+    return dec_batch_ws(nullptr, n_items, t).total;
+}
+
+int hc_seg_decompress_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_dec_item_t *items, uint32_t n_items,
+                                uint64_t *out_lens, int32_t *status, uint64_t *bad_segments, void *work,
+                                uint64_t work_bytes, void *stream)
+{
+    return decode_batch_dev(in, out, items, n_items, out_lens, status, bad_segments, work, work_bytes, stream, nullptr,
+                            nullptr);
+}
+
+int hc_seg_compress_host_batch(const uint8_t *const *in, const uint64_t *in_lens, const uint64_t *widths,
+                               uint32_t n_items, uint32_t flags, uint64_t seg_bytes, uint8_t *const *out,
+                               const uint64_t *out_caps, uint64_t *out_lens, int32_t *status)
+{
+    if (n_items == 0) return HC_OK;
+    if (!in || !in_lens || !out || !out_caps || !out_lens || !status) return HC_ERR_ARG;
+    if ((flags & ~kSegFlags) || (seg_bytes & 15u)) return HC_ERR_ARG;
+    const int use_adapt = (flags & HC_FLAG_ADAPT) ? 1 : 0;
+    if (use_adapt && !widths) return HC_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if ((!in[i] && in_lens[i]) || (!out[i] && out_caps[i])) return HC_ERR_ARG;
+    auto width = [&](uint32_t i) { return widths ? widths[i] : 512; };
+    std::vector<uint32_t> todo;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        out_lens[i] = 0;
+        status[i] = host_status(in_lens[i], use_adapt, width(i));
+        if (!status[i]) todo.push_back(i);
+    }
+    if (todo.empty()) return HC_OK;
+    if (!hc_device_ok()) {
+        for (uint32_t i : todo) status[i] = HC_ERR_DEVICE;
+        return HC_OK;
+    }
+    const uint64_t limit = pipe_bytes();
+    hipStream_t st = nullptr;
+    DevBuf din, dout, work, meta;
+    for (size_t a = 0; a < todo.size();) {
+        // the sub-batch [a, b): input bytes up to the limit, an item above it alone
+        size_t b = a;
+        uint64_t in_total = 0, out_total = 0;
+        std::vector<hc_seg_enc_item_t> items;
+        for (; b < todo.size(); ++b) {
+            const uint32_t i = todo[b];
+            if (b > a && in_total + in_lens[i] > limit) break;
+            const uint64_t cap = hc_seg_compress_bound2(in_lens[i], seg_bytes, flags, width(i));
+            if (cap == 0) return HC_ERR_ARG;  // (more segments than one call takes)
+            items.push_back(hc_seg_enc_item_t{in_total, in_lens[i], width(i), out_total, cap});
+            in_total += align16(in_lens[i]) + 16;
+            out_total += align16(cap);
+        }
+        const uint32_t m = (uint32_t)items.size();
+        const uint64_t wb = hc_seg_compress_batch_work_bound(items.data(), m, flags, seg_bytes);
+        if (wb == 0) return HC_ERR_ARG;
+        HC_CK(din.alloc(in_total));
+        HC_CK(dout.alloc(out_total + 16));
+        HC_CK(work.alloc(wb));
+        HC_CK(meta.alloc(12ull * m));
+        for (uint32_t j = 0; j < m; ++j)
+            if (items[j].in_len)
+                HC_CK(hipMemcpyAsync(din.as<uint8_t>() + items[j].in_off, in[todo[a + j]], items[j].in_len,
+                                     hipMemcpyHostToDevice, st));
+        uint64_t *d_lens = meta.as<uint64_t>();
+        int32_t *d_st = reinterpret_cast<int32_t *>(d_lens + m);
+        const int rc = hc_seg_compress_batch_dev(din.as<uint8_t>(), dout.as<uint8_t>(), items.data(), m, flags, seg_bytes,
+                                                 d_lens, d_st, work.p, wb, st);
+        if (rc) return rc;
+        std::vector<uint64_t> h_lens(m);
+        std::vector<int32_t> h_st(m);
+        HC_CK(hipMemcpyAsync(h_lens.data(), d_lens, 8ull * m, hipMemcpyDeviceToHost, st));
+        HC_CK(hipMemcpyAsync(h_st.data(), d_st, 4ull * m, hipMemcpyDeviceToHost, st));
+        HC_CK(hipStreamSynchronize(st));
+        for (uint32_t j = 0; j < m; ++j) {
+            const uint32_t i = todo[a + j];
+            status[i] = h_st[j];
+            if (h_st[j]) continue;
+            out_lens[i] = h_lens[j];
+            if (h_lens[j] > out_caps[i]) status[i] = HC_ERR_CAPACITY;
+            else HC_CK(hipMemcpy(out[i], dout.as<uint8_t>() + items[j].out_off, h_lens[j], hipMemcpyDeviceToHost));
+        }
+        a = b;
+    }
+    return HC_OK;
+}
+
+int hc_seg_decompress_host_batch(const uint8_t *const *in, const uint64_t *in_lens, const uint64_t *offsets,
+                                 const uint64_t *lengths, uint32_t n_items, uint8_t *const *out,
+                                 const uint64_t *out_caps, uint64_t *out_lens, int32_t *status, uint64_t *bad_segments)
+{
+    if (n_items == 0) return HC_OK;
+    if (!in || !in_lens || !out || !out_caps || !out_lens || !status) return HC_ERR_ARG;
+    if ((offsets == nullptr) != (lengths == nullptr)) return HC_ERR_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if ((!in[i] && in_lens[i]) || (!out[i] && out_caps[i])) return HC_ERR_ARG;
+    // what the host decides, in the single calls' order; the rest goes to the device
+    struct Todo {
+        uint32_t i;
+        hc_seg_dec_item_t item;       // in_off / out_off: set per sub-batch
+        uint64_t idx, s0, span, room;  // ranged: the upload is [0, idx) and [s0, s0 + span); whole: idx = in_len, span 0
+    };
+    std::vector<Todo> todo;
+    const bool device = hc_device_ok() != 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        out_lens[i] = 0;
+        status[i] = HC_OK;
+        if (bad_segments) bad_segments[i] = kNoSeg;
+        Todo t;
+        t.i = i;
+        if (hc_seg_info(in[i], in_lens[i], &t.item.info) != HC_OK) {
+            status[i] = HC_ERR_SEG_HEADER;
+            continue;
+        }
+        const hc_seg_info_t &info = t.item.info;
+        const bool whole = !lengths || (lengths[i] == HC_SEG_WHOLE && offsets[i] == 0);
+        Cuts c;
+        (void)info_ok(info, in_lens[i], c);
+        if (whole) {
+            if (c.n > kMaxSegs) status[i] = HC_ERR_ARG;
+            else if (!device) status[i] = HC_ERR_DEVICE;
+            if (status[i]) continue;
+            t.item = hc_seg_dec_item_t{0, in_lens[i], info, 0, HC_SEG_WHOLE, 0, out_caps[i]};
+            t.idx = in_lens[i];
+            t.s0 = t.span = 0;
+            t.room = out_caps[i] < info.raw_len ? out_caps[i] : info.raw_len;  // never more than raw_len is written
+        } else {
+            const uint64_t offset = offsets[i], length = lengths[i];
+            const bool check = checked(info.flags);
+            uint64_t s0 = 0, s1 = 0;
+            if (!range_ok(info.raw_len, offset, length) || c.n > kMaxSegs) status[i] = HC_ERR_ARG;
+            else if (hc_seg_index::index_scan(in[i], in_lens[i], c.n, check, range_cover(c, offset, length), &s0, &s1) != HC_OK)
+                status[i] = HC_ERR_SEG_HEADER;
+            else if (!device) status[i] = HC_ERR_DEVICE;
+            else if (out_caps[i] < length) {
+                status[i] = HC_ERR_CAPACITY;
+                out_lens[i] = length;
+            }
+            if (status[i]) continue;
+            t.item = hc_seg_dec_item_t{0, in_lens[i], info, offset, length, 0, length};
+            t.idx = align16(index_end(c.n, check));
+            t.s0 = s0;
+            t.span = s1 - s0;
+            t.room = length;
+        }
+        todo.push_back(t);
+    }
+    if (todo.empty()) return HC_OK;
+    const uint64_t limit = pipe_bytes();
+    hipStream_t st = nullptr;
+    DevBuf din, dout, work, meta;
+    for (size_t a = 0; a < todo.size();) {
+        // the sub-batch [a, b): uploaded bytes up to the limit, an item above it alone
+        size_t b = a;
+        uint64_t in_total = 0, out_total = 0;
+        std::vector<hc_seg_dec_item_t> items;
+        std::vector<uint64_t> skips, spans;
+        for (; b < todo.size(); ++b) {
+            Todo &t = todo[b];
+            const uint64_t up = t.idx + t.span;
+            if (b > a && in_total + up > limit) break;
+            t.item.in_off = in_total;
+            t.item.out_off = out_total;
+            items.push_back(t.item);
+            const bool ranged = t.item.length != HC_SEG_WHOLE;
+            skips.push_back(ranged ? t.s0 - t.idx : 0);
+            spans.push_back(ranged ? t.span : t.item.in_len);
+            in_total += align16(up) + 16;
+            out_total += align16(t.room) + 16;
+        }
+        const uint32_t m = (uint32_t)items.size();
+        DecTotals tot;
+        if (!dec_totals(items.data(), m, spans.data(), tot)) return HC_ERR_ARG;
+        const uint64_t wb = dec_batch_ws(nullptr, m, tot).total;
+        HC_CK(din.alloc(in_total));
+        HC_CK(dout.alloc(out_total));
+        HC_CK(work.alloc(wb));
+        HC_CK(meta.alloc(20ull * m));
+        for (uint32_t j = 0; j < m; ++j) {
+            const Todo &t = todo[a + j];
+            uint8_t *d = din.as<uint8_t>() + items[j].in_off;
+            if (t.idx) HC_CK(hipMemcpyAsync(d, in[t.i], t.idx, hipMemcpyHostToDevice, st));
+            if (t.span) HC_CK(hipMemcpyAsync(d + t.idx, in[t.i] + t.s0, t.span, hipMemcpyHostToDevice, st));
+        }
+        uint64_t *d_lens = meta.as<uint64_t>(), *d_bad = d_lens + m;
+        int32_t *d_st = reinterpret_cast<int32_t *>(d_bad + m);
+        const int rc = decode_batch_dev(din.as<uint8_t>(), dout.as<uint8_t>(), items.data(), m, d_lens, d_st, d_bad, work.p,
+                                        wb, st, skips.data(), spans.data());
+        if (rc) return rc;
+        std::vector<uint64_t> h(2ull * m);
+        std::vector<int32_t> h_st(m);
+        HC_CK(hipMemcpyAsync(h.data(), d_lens, 16ull * m, hipMemcpyDeviceToHost, st));
+        HC_CK(hipMemcpyAsync(h_st.data(), d_st, 4ull * m, hipMemcpyDeviceToHost, st));
+        HC_CK(hipStreamSynchronize(st));
+        for (uint32_t j = 0; j < m; ++j) {
+            const uint32_t i = todo[a + j].i;
+            status[i] = h_st[j];
+            out_lens[i] = h[j];
+            if (bad_segments) bad_segments[i] = h[m + j];
+            if (h_st[j] == 0 && h[j])
+                HC_CK(hipMemcpy(out[i], dout.as<uint8_t>() + items[j].out_off, h[j], hipMemcpyDeviceToHost));
+        }
+        a = b;
+    }
     return HC_OK;
 }
 

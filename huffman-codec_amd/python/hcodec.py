@@ -52,6 +52,22 @@ class SegInfo(ctypes.Structure):
     _fields_ = [("raw_len", ctypes.c_uint64), ("seg_bytes", ctypes.c_uint64), ("width", ctypes.c_uint64),
                 ("n_segments", ctypes.c_uint64), ("flags", ctypes.c_uint32)]
 
+HC_SEG_WHOLE = 2**64 - 1   # SegDecItem.length with offset 0: the whole container
+
+
+class SegEncItem(ctypes.Structure):
+    """hc_seg_enc_item_t: one input of a batched segmented encode"""
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_len", ctypes.c_uint64), ("width", ctypes.c_uint64),
+                ("out_off", ctypes.c_uint64), ("out_cap", ctypes.c_uint64)]
+
+
+class SegDecItem(ctypes.Structure):
+    """hc_seg_dec_item_t: one container and one range of it (0, HC_SEG_WHOLE: the whole)"""
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_len", ctypes.c_uint64), ("info", SegInfo),
+                ("offset", ctypes.c_uint64), ("length", ctypes.c_uint64),
+                ("out_off", ctypes.c_uint64), ("out_cap", ctypes.c_uint64)]
+
+
 SYNTH = {"noise": 0, "grad": 1, "photo": 2}
 
 _libs = {}           # path -> loaded library
@@ -150,6 +166,16 @@ def _load(path):
     L.hc_seg_decompress_range_work_bound.restype = u64
     L.hc_seg_decompress_range_dev.argtypes = [vp, u64, ctypes.POINTER(SegInfo), u64, u64, vp, u64, vp, vp, vp, vp, u64,
                                               vp]
+    L.hc_seg_compress_batch_work_bound.argtypes = [ctypes.POINTER(SegEncItem), ctypes.c_uint32, ctypes.c_uint32, u64]
+    L.hc_seg_compress_batch_work_bound.restype = u64
+    L.hc_seg_compress_batch_dev.argtypes = [vp, vp, ctypes.POINTER(SegEncItem), ctypes.c_uint32, ctypes.c_uint32, u64,
+                                            vp, vp, vp, u64, vp]
+    L.hc_seg_decompress_batch_work_bound.argtypes = [ctypes.POINTER(SegDecItem), ctypes.c_uint32]
+    L.hc_seg_decompress_batch_work_bound.restype = u64
+    L.hc_seg_decompress_batch_dev.argtypes = [vp, vp, ctypes.POINTER(SegDecItem), ctypes.c_uint32, vp, vp, vp, vp, u64,
+                                              vp]
+    L.hc_seg_compress_host_batch.argtypes = [vp, vp, vp, ctypes.c_uint32, ctypes.c_uint32, u64, vp, vp, vp, vp]
+    L.hc_seg_decompress_host_batch.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp, vp]
     _libs[path] = L
     return L
 
@@ -501,6 +527,138 @@ def seg_decompress_range_dev(inp, out, out_len, status, offset, length, bad_segm
     if rc:
         raise HCodecError(f"hc_seg_decompress_range_dev failed: {rc}")
     return work
+
+
+def _check_seg_batch(inp, out, n, out_lens, status, bad_segments):
+    """the tensor checks of _check_seg for the batched calls (one result per item)"""
+    import torch
+    spec = [("in", inp, torch.uint8, None), ("out", out, torch.uint8, None), ("out_lens", out_lens, torch.int64, n),
+            ("status", status, torch.int32, n)]
+    if bad_segments is not None:
+        spec.append(("bad_segments", bad_segments, torch.int64, n))
+    dev = inp.device if isinstance(inp, torch.Tensor) else None
+    for name, t, dt, numel in spec:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch tensor")
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"{name}: expected a CUDA tensor on {dev}, got {t.device}")
+        if t.dtype != dt:
+            raise TypeError(f"{name}: expected {dt}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: not contiguous")
+        if numel is not None and t.numel() != numel:
+            raise ValueError(f"{name}: {t.numel()} entries for {n} items")
+
+
+def seg_enc_items(items):
+    """a ctypes array of SegEncItem from (in_off, in_len, width, out_off, out_cap) tuples"""
+    return (SegEncItem * max(len(items), 1))(*[SegEncItem(*[int(v) for v in it]) for it in items])
+
+
+def seg_dec_items(items):
+    """a ctypes array of SegDecItem from (in_off, in_len, SegInfo, offset, length, out_off, out_cap)
+    tuples; a None info stays all zero, which the call answers with HC_ERR_SEG_HEADER"""
+    arr = (SegDecItem * max(len(items), 1))()
+    for a, (in_off, in_len, info, offset, length, out_off, out_cap) in zip(arr, items):
+        a.in_off, a.in_len, a.offset, a.length, a.out_off, a.out_cap = in_off, in_len, offset, length, out_off, out_cap
+        if info is not None:
+            a.info = info
+    return arr
+
+
+def seg_compress_batch_work_bound(items, use_diff=False, use_adapt=False, seg_bytes=0, check=False):
+    """hc_seg_compress_batch_work_bound of item tuples (seg_enc_items); 0: the call refuses them"""
+    return int(lib().hc_seg_compress_batch_work_bound(seg_enc_items(items), len(items),
+                                                      _seg_flags(use_diff, use_adapt, check), seg_bytes))
+
+
+def seg_decompress_batch_work_bound(items):
+    """hc_seg_decompress_batch_work_bound of item tuples (seg_dec_items)"""
+    return int(lib().hc_seg_decompress_batch_work_bound(seg_dec_items(items), len(items)))
+
+
+def seg_compress_batch_dev(inp, out, items, out_lens, status, use_diff=False, use_adapt=False, seg_bytes=0,
+                           check=False, stream=None, work=None):
+    """hc_seg_compress_batch_dev on CUDA tensors: item i, an (in_off, in_len, width, out_off,
+    out_cap) tuple, codes inp[in_off:+in_len] into one container at out[out_off:+out_cap];
+    out_lens (int64) and status (int32) hold one device result per item, asynchronous on
+    `stream`. The workspace is allocated here unless given. Returns it."""
+    n = len(items)
+    _check_seg_batch(inp, out, n, out_lens, status, None)
+    flags = _seg_flags(use_diff, use_adapt, check)
+    arr = seg_enc_items(items)
+    need = int(lib().hc_seg_compress_batch_work_bound(arr, n, flags, seg_bytes))
+    if work is None:
+        work = _work(need, inp.device)
+    rc = lib().hc_seg_compress_batch_dev(_dp(inp), _dp(out), arr, n, flags, seg_bytes, _dp(out_lens), _dp(status),
+                                         _dp(work), work.numel(), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_seg_compress_batch_dev failed: {rc}")
+    return work
+
+
+def seg_decompress_batch_dev(inp, out, items, out_lens, status, bad_segments=None, stream=None, work=None):
+    """hc_seg_decompress_batch_dev on CUDA tensors: item i, an (in_off, in_len, SegInfo, offset,
+    length, out_off, out_cap) tuple, reads raw bytes [offset, offset + length) of the container
+    at inp[in_off:+in_len] (0, HC_SEG_WHOLE: all of it) into out[out_off:+out_cap]. One device
+    result per item in out_lens, status and bad_segments. Returns the workspace."""
+    n = len(items)
+    _check_seg_batch(inp, out, n, out_lens, status, bad_segments)
+    arr = seg_dec_items(items)
+    need = int(lib().hc_seg_decompress_batch_work_bound(arr, n))
+    if work is None:
+        work = _work(need, inp.device)
+    rc = lib().hc_seg_decompress_batch_dev(_dp(inp), _dp(out), arr, n, _dp(out_lens), _dp(status),
+                                           ctypes.c_void_p(None) if bad_segments is None else _dp(bad_segments),
+                                           _dp(work), work.numel(), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_seg_decompress_batch_dev failed: {rc}")
+    return work
+
+
+def seg_compress_host_batch(blobs, use_diff=False, use_adapt=False, widths=None, seg_bytes=0, check=False, caps=None):
+    """hc_seg_compress_host_batch on host byte strings: (statuses, containers, out_lens); widths:
+    one per blob (default 512 each). caps: the output capacities (default: hc_seg_compress_bound2)."""
+    flags = _seg_flags(use_diff, use_adapt, check)
+    widths = [512] * len(blobs) if widths is None else widths
+    if caps is None:
+        caps = [lib().hc_seg_compress_bound2(len(b), seg_bytes if seg_bytes % 16 == 0 else 0, flags, w)
+                for b, w in zip(blobs, widths)]
+    w = (ctypes.c_uint64 * max(len(blobs), 1))(*[int(x) for x in widths])
+    L = lib()
+
+    def fn(ins, lens, n, outs, ocaps, olens, st):
+        return L.hc_seg_compress_host_batch(ins, lens, ctypes.cast(w, ctypes.c_void_p), n, flags, seg_bytes, outs,
+                                            ocaps, olens, st)
+    return _host_batch(fn, blobs, caps)
+
+
+def seg_decompress_host_batch(blobs, ranges=None, caps=None):
+    """hc_seg_decompress_host_batch on host byte strings: (statuses, decoded, out_lens,
+    bad_segments). ranges: None (every container whole) or one (offset, length) per blob; caps: the
+    output capacities (default: the range's length, or the header's raw_len)."""
+    n = len(blobs)
+    if caps is None:
+        caps = []
+        for k, b in enumerate(blobs):
+            if ranges is not None and tuple(ranges[k]) != (0, HC_SEG_WHOLE):
+                caps.append(ranges[k][1])
+            else:
+                st, info = seg_info(b)
+                caps.append(info.raw_len if st == 0 else 0)
+    offs = lens = ctypes.c_void_p(None)
+    if ranges is not None:
+        o = (ctypes.c_uint64 * max(n, 1))(*[int(r[0]) for r in ranges])
+        m = (ctypes.c_uint64 * max(n, 1))(*[int(r[1]) for r in ranges])
+        offs, lens = ctypes.cast(o, ctypes.c_void_p), ctypes.cast(m, ctypes.c_void_p)
+    bad = (ctypes.c_uint64 * max(n, 1))()
+    L = lib()
+
+    def fn(ins, ilens, n_items, outs, ocaps, olens, st):
+        return L.hc_seg_decompress_host_batch(ins, ilens, offs, lens, n_items, outs, ocaps, olens, st,
+                                              ctypes.cast(bad, ctypes.c_void_p))
+    sts, res, olens = _host_batch(fn, blobs, caps)
+    return sts, res, olens, [bad[i] for i in range(n)]
 
 
 def crc32_batch(inp, in_offs, lens, crc, stream=None):

@@ -367,6 +367,101 @@ int hc_seg_decompress_range_dev(const uint8_t *in, uint64_t in_len, const hc_seg
                                 uint64_t *out_len, int32_t *status, uint64_t *bad_segment,
                                 void *work, uint64_t work_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Batches of containers: many inputs, or many (container, range) pairs, in one call whose
+ * launches do not grow with the number of items (a directory of mid-sized files; a viewer that
+ * fetches many regions of one large image). A launch of the coders takes about as long as its
+ * longest segment's serial chain whatever it holds, so n items in one launch cost about one.
+ *
+ * An encoder item is one input; a decoder item is one container and one range of it, or the whole
+ * (length == HC_SEG_WHOLE with offset 0: exactly hc_seg_decompress_dev, an empty container's one
+ * empty segment included). The same container may be named by several decoder items. One decode
+ * call may mix plain, -m, adaptive, checked and unchecked containers: they describe themselves.
+ * The encoder's flags and seg_bytes hold for the whole call; width is per item: 0 is
+ * HC_ERR_WIDTH as in every encoder, and any other value is read only with HC_FLAG_ADAPT.
+ *
+ * The equivalence rule: for every item, the bytes written, out_lens[i], status[i] and
+ * bad_segments[i] are exactly what hc_seg_compress_dev, hc_seg_decompress_dev or
+ * hc_seg_decompress_range_dev gives for that item alone with the same arguments, by the
+ * precedence documented for those calls. What such a call reports through its return value for a
+ * reason that belongs to the item goes to status[i] instead: HC_ERR_WIDTH, HC_ERR_MATRIX_SIZE,
+ * HC_ERR_DIMS, a range outside raw_len (HC_ERR_ARG), an info that fails the rules
+ * (HC_ERR_SEG_HEADER); then out_lens[i] = 0, bad_segments[i] = UINT64_MAX, and the item launches
+ * nothing and touches no output byte. Items are independent: a damaged segment, too small an
+ * out_cap or a bad header changes nothing about any other item. No byte is written outside
+ * out[out_off .. out_off + out_cap) of an item, and for a decoder item none outside its first
+ * `length` bytes, whatever the status. Output ranges must not overlap; input ranges may.
+ *
+ * Memory. `items` is HOST memory, read before the call returns and never after (the descriptors
+ * travel as kernel arguments, so a call can be captured in a graph). in, out, work, out_lens,
+ * status and bad_segments (may be NULL) are DEVICE pointers; in, out, work and every in_off /
+ * out_off are 16-byte aligned. As in the single calls: asynchronous on `stream`, no allocation, no
+ * host synchronisation, no host read of device memory, every byte of scratch from `work`.
+ *
+ * The return value reports call-level errors only, and then nothing is launched or written:
+ * HC_ERR_ARG for a null pointer, a misaligned base or offset, a flag outside HC_FLAG_DIFF |
+ * HC_FLAG_ADAPT | HC_SEG_CHECK_CRC32, seg_bytes not a multiple of 16, work_bytes below the bound,
+ * or more than 2^31 - 1 segments in the call (in any one container, for the decoder);
+ * HC_ERR_DEVICE for a launch error. n_items == 0 does nothing and returns HC_OK.
+ *
+ * Work bounds (0 for arguments that the call refuses), a16(x) = x rounded up to a multiple of 16.
+ * Encoder, over the items whose width / length pass hc_compress's checks, with N their segments
+ * in total (hc_seg_count), S the sum of a16(hc_compress_bound(segment, adapt)) over those
+ * segments and R the sum of their in_len:
+ *   7 a16(8 N) + a16(4 N) [+ a16(4 N) checked] + 16 + S
+ *   [+ a16(hc_adapt_compress_work_bound(R, N)) adaptive, N > 0]
+ *   + a16(112 n_items) + a16(4 N) + a16(8 n_items)
+ * Decoder, over the items whose info and range pass, with C their covered segments in total (a
+ * whole item: all n), L their staging slots and B the slots' bytes as the range bound above
+ * counts them per item, and for the adaptive items E the sum of in_len, W the raw bytes of their
+ * covered segments and A their count:
+ *   5 a16(8 C) + 2 a16(4 C) + a16(8 n_items) + a16(176 n_items) + 3 a16(8 L) + B
+ *   [+ a16(hc_adapt_decompress_work_bound(E, W, A)) when A > 0]
+ * Both grow with every item added and are at least the single call's bound for each item.
+ * ------------------------------------------------------------------------------------- */
+#define HC_SEG_WHOLE UINT64_MAX
+typedef struct hc_seg_enc_item_t {
+    uint64_t in_off, in_len; /* the input: in[in_off .. in_off + in_len) */
+    uint64_t width;          /* the matrix width (HC_FLAG_ADAPT only) */
+    uint64_t out_off, out_cap;
+} hc_seg_enc_item_t;
+typedef struct hc_seg_dec_item_t {
+    uint64_t in_off, in_len; /* the container: in[in_off .. in_off + in_len) */
+    hc_seg_info_t info;      /* hc_seg_info of its first 48 bytes, from the host */
+    uint64_t offset, length; /* the range, or 0 and HC_SEG_WHOLE */
+    uint64_t out_off, out_cap;
+} hc_seg_dec_item_t;
+
+uint64_t hc_seg_compress_batch_work_bound(const hc_seg_enc_item_t *items, uint32_t n_items, uint32_t flags,
+                                          uint64_t seg_bytes);
+int hc_seg_compress_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_enc_item_t *items, uint32_t n_items,
+                              uint32_t flags, uint64_t seg_bytes, uint64_t *out_lens, int32_t *status,
+                              void *work, uint64_t work_bytes, void *stream);
+uint64_t hc_seg_decompress_batch_work_bound(const hc_seg_dec_item_t *items, uint32_t n_items);
+int hc_seg_decompress_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_dec_item_t *items, uint32_t n_items,
+                                uint64_t *out_lens, int32_t *status, uint64_t *bad_segments,
+                                void *work, uint64_t work_bytes, void *stream);
+
+/* Host buffers, synchronous: item i reads in[i][0 .. in_lens[i]) and writes out[i][0 .. out_caps[i]).
+ * The items go to the device in sub-batches of at most HC_PIPE_BYTES uploaded bytes (the host-buffer
+ * batch API's variable; an item above it goes alone), one device call per sub-batch on the cached
+ * scratch of the single calls. status[i], out_lens[i] and bad_segments[i] (may be NULL) are what
+ * hc_seg_compress2, hc_seg_decompress or hc_seg_decompress_range reports for item i alone, its
+ * return value as status[i] (HC_ERR_DEVICE without a device included; out_lens[i] is 0 where that
+ * call leaves *out_len unset). offsets and lengths both NULL: every item whole; an item with
+ * lengths[i] == HC_SEG_WHOLE and offsets[i] == 0 is whole too. A ranged item keeps
+ * hc_seg_decompress_range's properties: its index is checked on the host, only the header, the
+ * index and the covered segments' bytes are uploaded, and only `length` bytes come back. The
+ * return value: HC_ERR_ARG (a null array, one of offsets / lengths alone, a bad flag, seg_bytes
+ * not a multiple of 16, too many segments) or HC_ERR_DEVICE (a HIP error), else HC_OK. */
+int hc_seg_compress_host_batch(const uint8_t *const *in, const uint64_t *in_lens, const uint64_t *widths,
+                               uint32_t n_items, uint32_t flags, uint64_t seg_bytes, uint8_t *const *out,
+                               const uint64_t *out_caps, uint64_t *out_lens, int32_t *status);
+int hc_seg_decompress_host_batch(const uint8_t *const *in, const uint64_t *in_lens, const uint64_t *offsets,
+                                 const uint64_t *lengths, uint32_t n_items, uint8_t *const *out,
+                                 const uint64_t *out_caps, uint64_t *out_lens, int32_t *status,
+                                 uint64_t *bad_segments);
+
 /* CRC-32 (zlib's crc32: reflected polynomial 0xEDB88320, init and final xor 0xFFFFFFFF) of
  * n_ranges byte ranges, the kernel behind the checked container: crc[i] of in[in_offs[i] ..
  * +lens[i]). DEVICE pointers, asynchronous on `stream`; any alignment, any length (0: crc 0), any

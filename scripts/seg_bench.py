@@ -18,6 +18,15 @@ on both sides), median of the repeats after warm-up. Prints one JSON line.
                                              1 MiB at a multiple of 4 and the same 1 MiB one byte on
                                              (every covered segment staged); --big adds a 16384x16384
                                              photo (4096 segments of 64 KiB)
+  scripts/seg_bench.py --batch               many items per call (hc_seg_*_host_batch) against a loop of
+                                             single calls in the same process: 4, 16 and 64 inputs of
+                                             1 MiB (128 rows of a 8192x8192 photo each) at 64 KiB
+                                             segments in -m and -a -m, encode and decode, and 64 ranged
+                                             reads of 4 KiB out of one 4096x4096 container as one call
+                                             against 64; with --trace-run the batch calls alone, twice
+                                             at every N, so that a kernel's call count shows whether
+                                             its launches grow with N (`rocprofv3 --kernel-trace --stats
+                                             --output-format csv`, kernel trace alone, no counters)
   scripts/seg_bench.py --trace-run           a few segmented calls only, to be run under
                                              `rocprofv3 --kernel-trace --stats -- python ...`
   scripts/seg_bench.py --glue-from STATS.csv adds the glue kernels' share of device time, read
@@ -41,7 +50,9 @@ SIDE = 4096
 MODES = {"-m": (1, 0), "-a -m": (1, 1), "-a": (0, 1)}
 SIZES = (16384, 65536, 262144)
 GLUE = ("seg_plan_kernel", "seg_seal_kernel", "seg_gather_kernel", "seg_open_kernel", "seg_close_kernel",
-        "crc32_kernel", "pack_kernel")
+        "crc32_kernel", "pack_kernel", "seg_items_kernel", "seg_plan_batch_kernel", "seg_seal_batch_kernel",
+        "seg_gather_batch_kernel", "seg_open_batch_kernel", "seg_close_batch_kernel")
+BATCH_SIDE, BATCH_ITEM, BATCH_NS = 8192, 1 << 20, (4, 16, 64)
 
 
 def photo(side=SIDE):
@@ -200,6 +211,115 @@ def range_bench(raw, side, diff, adapt, seg, reps, device):
     return res
 
 
+def _ptrs(bufs):
+    return (ctypes.c_void_p * len(bufs))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
+
+
+def _u64s(vals):
+    return (ctypes.c_uint64 * len(vals))(*vals)
+
+
+def batch_containers(raw, diff, adapt, n, reps, trace):
+    """n inputs of BATCH_ITEM bytes through one hc_seg_*_host_batch call and through n single calls"""
+    L = hc.lib()
+    seg = 65536
+    flags = (hc.HC_FLAG_DIFF if diff else 0) | (hc.HC_FLAG_ADAPT if adapt else 0)
+    pieces = [raw[k * BATCH_ITEM:(k + 1) * BATCH_ITEM] for k in range(n)]
+    cap = int(L.hc_seg_compress_bound2(BATCH_ITEM, seg, flags, BATCH_SIDE))
+    ins = [ctypes.c_char_p(p) for p in pieces]
+    encs = [ctypes.create_string_buffer(cap) for _ in range(n)]
+    decs = [ctypes.create_string_buffer(BATCH_ITEM) for _ in range(n)]
+    in_p, enc_p, dec_p = _ptrs(ins), _ptrs(encs), _ptrs(decs)
+    in_lens, widths, caps, raw_caps = (_u64s([v] * n) for v in (BATCH_ITEM, BATCH_SIDE, cap, BATCH_ITEM))
+    enc_lens, dec_lens = _u64s([0] * n), _u64s([0] * n)
+    st = (ctypes.c_int32 * n)()
+    k = ctypes.c_uint64(0)
+
+    def enc_batch():
+        rc = L.hc_seg_compress_host_batch(in_p, in_lens, widths, n, flags, seg, enc_p, caps, enc_lens, st)
+        assert rc == 0 and not any(st), (rc, list(st))
+
+    def dec_batch():
+        rc = L.hc_seg_decompress_host_batch(enc_p, enc_lens, None, None, n, dec_p, raw_caps, dec_lens, st, None)
+        assert rc == 0 and not any(st), (rc, list(st))
+
+    def enc_loop():
+        for i in range(n):
+            rc = L.hc_seg_compress2(in_p[i], BATCH_ITEM, flags, BATCH_SIDE, seg, enc_p[i], cap, ctypes.byref(k))
+            assert rc == 0 and k.value == enc_lens[i], rc
+
+    def dec_loop():
+        for i in range(n):
+            rc = L.hc_seg_decompress(enc_p[i], enc_lens[i], dec_p[i], BATCH_ITEM, ctypes.byref(k), None)
+            assert rc == 0 and k.value == BATCH_ITEM, rc
+
+    if trace:
+        for _ in range(2):
+            enc_batch()
+            dec_batch()
+        return None
+    enc_batch()
+    batch_enc = [e.raw[:m] for e, m in zip(encs, enc_lens)]
+    r = {"items": n, "bytes": sum(enc_lens), "segments_per_item": hc.seg_count(BATCH_ITEM, seg, adapt, BATCH_SIDE)}
+    r["encode_batch_ms"] = timed(enc_batch, 2, reps)
+    r["encode_loop_ms"] = timed(enc_loop, 1, reps)
+    assert [e.raw[:m] for e, m in zip(encs, enc_lens)] == batch_enc  # the loop wrote the same containers
+    for d in decs:
+        ctypes.memset(d, 0, BATCH_ITEM)
+    r["decode_batch_ms"] = timed(dec_batch, 2, reps)
+    assert all(d.raw == p for d, p in zip(decs, pieces))
+    r["decode_loop_ms"] = timed(dec_loop, 1, reps)
+    r["encode_speedup"] = round(r["encode_loop_ms"][0] / r["encode_batch_ms"][0], 2)
+    r["decode_speedup"] = round(r["decode_loop_ms"][0] / r["decode_batch_ms"][0], 2)
+    return r
+
+
+def batch_ranges(raw, reps, trace, reads=64, length=4096):
+    """`reads` ranged reads of one 4096x4096 -m container at 64 KiB segments: one call against a loop"""
+    L = hc.lib()
+    st, enc = hc.seg_compress(raw, True, False, SIDE, 65536)
+    assert st == 0, st
+    ranges = [(k * (len(raw) // reads) + 8192, length) for k in range(reads)]  # each inside one segment
+    src = ctypes.c_char_p(enc)
+    outs = [ctypes.create_string_buffer(length) for _ in range(reads)]
+    in_p, out_p = _ptrs([src] * reads), _ptrs(outs)
+    in_lens, caps = _u64s([len(enc)] * reads), _u64s([length] * reads)
+    offs, lens, out_lens = _u64s([o for o, _ in ranges]), _u64s([m for _, m in ranges]), _u64s([0] * reads)
+    stt = (ctypes.c_int32 * reads)()
+    k = ctypes.c_uint64(0)
+
+    def batch():
+        rc = L.hc_seg_decompress_host_batch(in_p, in_lens, offs, lens, reads, out_p, caps, out_lens, stt, None)
+        assert rc == 0 and not any(stt), (rc, list(stt))
+
+    def loop():
+        for i, (o, m) in enumerate(ranges):
+            rc = L.hc_seg_decompress_range(in_p[i], len(enc), o, m, out_p[i], m, ctypes.byref(k), None)
+            assert rc == 0 and k.value == m, rc
+
+    if trace:
+        batch()
+        batch()
+        return None
+    r = {"reads": reads, "length": length, "container_bytes": len(enc), "batch_ms": timed(batch, 2, reps)}
+    assert all(b.raw == raw[o:o + m] for b, (o, m) in zip(outs, ranges))
+    r["loop_ms"] = timed(loop, 1, reps)
+    r["speedup"] = round(r["loop_ms"][0] / r["batch_ms"][0], 2)
+    return r
+
+
+def batch_bench(reps, trace):
+    big = photo(BATCH_SIDE)
+    res = {"input": f"{BATCH_ITEM}-byte pieces ({BATCH_ITEM // BATCH_SIDE} rows) of a synthetic photo {BATCH_SIDE}x{BATCH_SIDE}, "
+                    "64 KiB segments", "timing": "host clock around each synchronous host-buffer call or loop of calls "
+                    "(copies included), median [min, max] ms of %d" % reps, "containers": {}}
+    for name, (diff, adapt) in (("-m", (1, 0)), ("-a -m", (1, 1))):
+        for n in BATCH_NS:
+            res["containers"][f"{name} x{n}"] = batch_containers(big, diff, adapt, n, reps, trace)
+    res["ranges"] = batch_ranges(photo(), reps, trace)
+    return res
+
+
 def full_bytes(seg, adapt, width):
     """raw bytes of every segment but the last (the cut rule of include/hcodec.h)"""
     return max(8, (seg // width) & ~3) * width if adapt else seg
@@ -232,9 +352,18 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=list(SIZES))
     ap.add_argument("--range", action="store_true")
     ap.add_argument("--big", action="store_true")
+    ap.add_argument("--batch", action="store_true")
     a = ap.parse_args()
     if not hc.device_ok():
         sys.exit("seg_bench.py needs a gfx950 device: " + hc.device_info())
+    if a.batch:
+        res = batch_bench(a.reps, a.trace_run)
+        if a.trace_run:
+            return
+        if a.glue_from:
+            res["glue"] = glue_share(a.glue_from)
+        print(json.dumps(res))
+        return
     if a.range:
         raw = photo()
         if a.trace_run:
