@@ -54,12 +54,10 @@ uint64_t adapt_encode_work_bound(uint64_t total_in, uint32_t n);
 uint64_t adapt_decode_work_bound(uint64_t total_in, uint64_t total_out, uint32_t n);
 
 // CRC-32 of n byte ranges in[offs[i] .. +lens[i]) into crc[i] (hc_crc.hip), asynchronous on st.
-// With a gate (the segmented decoder's; all three pointers or none) nothing at all is read when
-// ctl[0] != 0, and range i is skipped, crc[i] left alone, unless status[i] == 0 and
-// got_lens[i] == lens[i]. A null ctl with the other two set (the batched decoder, whose verdicts
-// are per item and reach the segments' status) leaves the per-range test alone.
+// With a gate (the segmented decoder's; both pointers or none) range i is skipped, crc[i] left
+// alone, unless status[i] == 0 and got_lens[i] == lens[i]. (The decoder's verdicts are per item
+// and reach the segments' status: an item that may not be read has no segment with status 0.)
 struct CrcGate {
-    const uint64_t *ctl;
     const int32_t *status;
     const uint64_t *got_lens;
 };

@@ -22,10 +22,13 @@
 //           for the covered segments only; one that the range covers in part, or any at an offset
 //           that is no multiple of 4, decodes into a slot of the workspace, and a pack launch
 //           (hc_pipe.hip) moves its covered part to its place in out before seg_close
-//   batch   many inputs, or many (container, range) pairs, per call (hc_seg_*_batch_dev): the
-//           segments of all items in one concatenated array, so the same coder launches serve
-//           them all; the glue kernels per item (the *_batch_kernel forms further down), the item
-//           records carried to the device as kernel arguments by seg_items_kernel
+//   items   a call codes one item (an input, or a container and a range of it) or many
+//           (hc_seg_*_batch_dev): the segments of all items lie in one concatenated array, so the
+//           same coder launches serve them all. Each glue stage above is written once, against an
+//           item record (EncItem, DecItem) that it gets from an item source: One, a single call's
+//           record in the kernel arguments, or Many, a batch's records in the workspace, carried
+//           there as kernel arguments by seg_items_kernel. Seal, open and close run one workgroup
+//           per item.
 //
 // Every launch is asynchronous on the caller's stream; no allocation, no host synchronisation,
 // no host read of device memory in the device entry points. A container-level error zeroes
@@ -65,22 +68,6 @@ using hc_seg_index::kSegFlags;
 using hc_seg_index::range_cover;
 using hc_seg_index::range_ok;
 using hc_seg_index::seg_cuts;
-
-// the 48 header bytes as six little-endian words (what the device holds at in / out + 0..47)
-struct Header {
-    uint64_t w[6];
-};
-Header make_header(uint32_t flags, uint64_t raw_len, uint64_t seg_bytes, uint64_t width, uint64_t n)
-{
-    Header h;
-    h.w[0] = get64(kMagic);
-    h.w[1] = flags & 0xFFFFu;  // byte 8 the flags, byte 9 the check kind
-    h.w[2] = raw_len;
-    h.w[3] = seg_bytes;
-    h.w[4] = width;
-    h.w[5] = n;
-    return h;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Workspace layouts (host-side carving; every region 16-byte aligned)
@@ -152,125 +139,7 @@ __device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t *part, uint6
     return sat_add(before, excl);
 }
 
-struct PlanArgs {
-    uint64_t *in_offs, *in_lens, *widths, *out_offs, *out_caps, *out_lens;
-    int32_t *status;
-    uint64_t n, full, last, slot_full, cap_full, cap_last, width;
-};
-
-// segment k's input range and its output slot (all in closed form: only the last segment differs)
-__global__ __launch_bounds__(256) void seg_plan_kernel(PlanArgs a)
-{
-    const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= a.n) return;
-    const bool tail = k == a.n - 1;
-    a.in_offs[k] = k * a.full;
-    a.in_lens[k] = tail ? a.last : a.full;
-    a.widths[k] = a.width;
-    a.out_offs[k] = k * a.slot_full;
-    a.out_caps[k] = tail ? a.cap_last : a.cap_full;
-    a.out_lens[k] = 0;
-    a.status[k] = HC_ERR_DEVICE;  // every segment is coded by exactly one launch, which overwrites this
-}
-
-struct SealArgs {
-    const uint64_t *enc_lens;
-    const int32_t *seg_status;
-    const uint32_t *crc;  // null: an unchecked container
-    uint64_t *dst_offs, *ctl;
-    uint64_t n;
-    uint8_t *out;
-    uint64_t out_cap;
-    uint64_t *out_len;
-    int32_t *status;
-    Header hdr;
-};
-
-__global__ __launch_bounds__(kScan) void seg_seal_kernel(SealArgs a)
-{
-    __shared__ uint64_t part[kScan / 64];
-    __shared__ unsigned long long s_bad, s_end;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) {
-        s_bad = kNoSeg;
-        s_end = 0;
-    }
-    __syncthreads();
-    const uint64_t idx_end = index_end(a.n, a.crc != nullptr);
-    uint64_t carry = align16(idx_end);  // where segment 0 starts
-    uint64_t bad = kNoSeg;
-    for (uint64_t base = 0; base < a.n; base += kScan) {
-        const uint64_t k = base + tid;
-        const bool in = k < a.n;
-        const uint64_t len = in ? a.enc_lens[k] : 0;
-        if (in && a.seg_status[k] != 0 && bad == kNoSeg) bad = k;
-        uint64_t total;
-        const uint64_t off = sat_add(carry, block_scan(in ? align16(len) : 0, part, total));
-        if (in) a.dst_offs[k] = off;
-        if (in && k == a.n - 1) s_end = sat_add(off, len);  // no padding after the last segment
-        carry = sat_add(carry, total);
-    }
-    if (bad != kNoSeg) atomicMin(&s_bad, (unsigned long long)bad);
-    __syncthreads();
-    const uint64_t first_bad = s_bad, end = s_end;
-    int32_t st = 0;
-    if (first_bad != kNoSeg) st = a.seg_status[first_bad];
-    else if (end > a.out_cap) st = HC_ERR_CAPACITY;
-    if (tid == 0) {
-        *a.status = st;
-        *a.out_len = (st == 0 || st == HC_ERR_CAPACITY) ? end : 0;
-        a.ctl[0] = st == 0 ? 1 : 0;
-    }
-    if (st != 0) return;
-    // sealed: end <= out_cap, so the header, the index and its padding lie inside out
-    uint64_t *o64 = reinterpret_cast<uint64_t *>(a.out);
-    uint32_t *o32 = reinterpret_cast<uint32_t *>(a.out);
-    if (tid < 6) o64[tid] = a.hdr.w[tid];
-    // the index ends on a multiple of 4: zero words up to segment 0
-    if (tid >= 8 && tid < 8 + (align16(idx_end) - idx_end) / 4) o32[idx_end / 4 + (tid - 8)] = 0;
-    for (uint64_t k = tid; k < a.n; k += kScan) o64[6 + k] = a.enc_lens[k];
-    if (a.crc)
-        for (uint64_t k = tid; k < a.n; k += kScan) o32[12 + 2 * a.n + k] = a.crc[k];
-}
-
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// Slot k -> out + dst_offs[k], one workgroup per segment. Both ends are 16-byte aligned, so whole
-// 16-byte chunks per lane; the chunk that holds the stream's last bytes goes out with its
-// padding zeroed, except the last segment's (the container ends with its last byte: bytes).
-__global__ __launch_bounds__(256) void seg_gather_kernel(const uint8_t *slots, const uint64_t *slot_offs,
-                                                         const uint64_t *enc_lens, const uint64_t *dst_offs,
-                                                         const uint64_t *ctl, uint64_t n, uint8_t *out)
-{
-    if (ctl[0] == 0) return;  // not sealed: nothing is copied
-    for (uint64_t k = blockIdx.x; k < n; k += gridDim.x) {
-        const uint64_t len = enc_lens[k];
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(slots + slot_offs[k]);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(out + dst_offs[k]);
-        const uint64_t chunks = len / 16;
-        for (uint64_t c = threadIdx.x; c < chunks; c += 256) dst[c] = src[c];
-        const uint32_t rem = (uint32_t)(len & 15u);
-        if (rem == 0 || threadIdx.x != 255) continue;
-        if (k == n - 1) {
-            const uint8_t *s8 = reinterpret_cast<const uint8_t *>(src + chunks);
-            uint8_t *d8 = reinterpret_cast<uint8_t *>(dst + chunks);
-            for (uint32_t b = 0; b < rem; ++b) d8[b] = s8[b];
-        } else {
-            u32x4 v = src[chunks];  // inside the slot: slots are multiples of 16 bytes
-            uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (uint32_t d = 0; d < 4; ++d) {
-                if (rem <= 4 * d) w[d] = 0;
-                else if (rem < 4 * d + 4) w[d] &= (1u << (8 * (rem - 4 * d))) - 1u;
-            }
-            v.x = w[0];
-            v.y = w[1];
-            v.z = w[2];
-            v.w = w[3];
-            dst[chunks] = v;
-        }
-    }
-}
 
 // hc_seg_decompress_dev with an info that fails the host checks: the verdict alone
 __global__ void seg_reject_kernel(uint64_t *out_len, int32_t *status, uint64_t *bad_segment)
@@ -290,44 +159,6 @@ __global__ void seg_reject_kernel(uint64_t *out_len, int32_t *status, uint64_t *
 // starts inside it, then one for the last covered segment when the range ends inside it (none for
 // the whole decoder); of an unaligned range: slot s for segment k0 + s.
 // ---------------------------------------------------------------------------------------------
-struct DecWs {
-    uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;
-    int32_t *status;
-    uint32_t *crc;  // checked containers: the decoded segments' CRC-32 (otherwise no bytes)
-    uint64_t *ctl;  // [0] the container-level status (0, HC_ERR_SEG_HEADER, HC_ERR_CAPACITY)
-    uint64_t *cp_src, *cp_len, *cp_dst;  // slot s: cp_len[s] bytes from slots + cp_src[s] to out + cp_dst[s]
-    uint8_t *slots;
-    void *awork;
-    uint64_t awork_bytes, total;
-};
-DecWs carve_dec(void *work, uint64_t count, uint64_t nslots, uint64_t slot, uint64_t awork_bytes, bool check)
-{
-    DecWs w;
-    uint8_t *p = static_cast<uint8_t *>(work);
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p ? p + o : nullptr;  // null: sizing only
-        o += align16(bytes);
-        return q;
-    };
-    w.in_offs = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.in_lens = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.out_offs = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.out_caps = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.out_lens = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.status = reinterpret_cast<int32_t *>(take(4 * count));
-    w.crc = reinterpret_cast<uint32_t *>(take(check ? 4 * count : 0));
-    w.ctl = reinterpret_cast<uint64_t *>(take(16));
-    w.cp_src = reinterpret_cast<uint64_t *>(take(8 * nslots));
-    w.cp_len = reinterpret_cast<uint64_t *>(take(8 * nslots));
-    w.cp_dst = reinterpret_cast<uint64_t *>(take(8 * nslots));
-    w.slots = take(nslots * slot);
-    w.awork = take(awork_bytes);
-    w.awork_bytes = awork_bytes;
-    w.total = o;
-    return w;
-}
-
 // the sizes of a range inside raw_len; whole: the range (0, raw_len) over all n segments (an empty
 // container's one empty segment included, which the empty range would not cover)
 struct DecPlan {
@@ -350,131 +181,6 @@ DecPlan dec_plan(const Cuts &c, uint64_t offset, uint64_t length, bool whole)
         p.nslots = p.cv.count == 1 ? (head || tail) : (uint64_t)head + tail;
     }
     return p;
-}
-
-struct OpenArgs {
-    const uint8_t *in;
-    uint64_t in_len, skip;  // skip: what the covered segments' input offsets lose (a compact upload)
-    Header hdr;             // the caller's host copy (checked on the host already)
-    uint64_t n, full, last, offset, length, out_cap;
-    uint64_t k0, count, nslots, slot;
-    uint64_t out_d, slot_d;  // out and the slots from the batch's output base
-    uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;
-    uint64_t *cp_src, *cp_len, *cp_dst;
-    int32_t *status;
-    uint64_t *ctl;
-    bool check;
-};
-
-// The host has checked its copy of the header against in_len (48 + 8 n <= in_len among the rest;
-// 12 n in a checked container, whose crc words follow the lengths); here the device bytes must
-// equal that copy, and the index must tile [align16(48 + 8 n or 12 n), in_len) exactly, whatever
-// the range. enc_len entries are untrusted: the offsets add with saturation and every range is
-// compared by subtraction, so a forged length cannot wrap into a valid offset. Segment arrays for
-// the covered segments only (entry k - k0), and the staged ones' copies.
-__global__ __launch_bounds__(kScan) void seg_open_kernel(OpenArgs a)
-{
-    __shared__ uint64_t part[kScan / 64];
-    __shared__ uint32_t s_err;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) s_err = 0;
-    for (uint64_t s = tid; s < a.nslots; s += kScan) a.cp_len[s] = 0;  // a slot nothing is staged in
-    __syncthreads();
-    bool err = false;
-    const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in);
-    if (tid < 6 && i64[tid] != a.hdr.w[tid]) err = true;
-    const uint64_t end = a.offset + a.length;  // (inside raw_len: the host's check)
-    const bool all_staged = (a.offset & 3u) != 0;
-    const uint64_t tail_slot = a.offset != a.k0 * a.full;  // aligned: after segment k0's slot, if it has one
-    uint64_t carry = align16(index_end(a.n, a.check));
-    for (uint64_t base = 0; base < a.n; base += kScan) {
-        const uint64_t k = base + tid;
-        const bool in = k < a.n;
-        const uint64_t len = in ? i64[6 + k] : 0;
-        const bool big = len > a.in_len;
-        uint64_t total;
-        const uint64_t off = sat_add(carry, block_scan(in && !big ? align16(len) : 0, part, total));
-        if (in) {
-            const bool tail = k == a.n - 1;
-            if (big || off > a.in_len || len > a.in_len - off) err = true;
-            else if (tail && off + len != a.in_len) err = true;  // truncated, or trailing bytes
-        }
-        if (in && k >= a.k0 && k - a.k0 < a.count) {
-            const uint64_t i = k - a.k0;
-            const uint64_t b = k * a.full, cap = k == a.n - 1 ? a.last : a.full, e = b + cap;
-            const uint64_t lo = b > a.offset ? b : a.offset, hi = e < end ? e : end;
-            a.in_offs[i] = off - a.skip;  // (a wrapped value is never read: err zeroes in_lens)
-            a.in_lens[i] = len;
-            a.out_caps[i] = cap;
-            a.out_lens[i] = 0;
-            a.status[i] = HC_ERR_DEVICE;  // overwritten by the launch that owns the segment
-            if (all_staged || lo != b || hi != e) {
-                const uint64_t s = all_staged ? i : (i == 0 ? 0 : tail_slot);
-                a.out_offs[i] = a.slot_d + s * a.slot;
-                a.cp_src[s] = s * a.slot + (lo - b);
-                a.cp_len[s] = hi - lo;
-                a.cp_dst[s] = lo - a.offset;
-            } else {
-                a.out_offs[i] = a.out_d + (b - a.offset);
-            }
-        }
-        carry = sat_add(carry, total);
-    }
-    if (err) s_err = 1;
-    __syncthreads();
-    const int32_t st = s_err ? HC_ERR_SEG_HEADER : (a.length > a.out_cap ? HC_ERR_CAPACITY : 0);
-    if (tid == 0) a.ctl[0] = (uint64_t)st;
-    if (st == 0) return;
-    // nothing may be decoded or copied: empty inputs, which the coders answer with HC_ERR_HEADER
-    // before they touch anything, and empty copies
-    for (uint64_t i = tid; i < a.count; i += kScan) a.in_lens[i] = 0;
-    for (uint64_t s = tid; s < a.nslots; s += kScan) a.cp_len[s] = 0;
-}
-
-struct CloseArgs {
-    const uint64_t *out_lens, *out_caps, *ctl;
-    const int32_t *seg_status;
-    const uint32_t *crc, *want_crc;  // checked containers: of the decoded bytes, and the index's from k0 (else null)
-    uint64_t k0, count, length;
-    uint64_t *out_len, *bad_segment;
-    int32_t *status;
-};
-
-// the verdict over the covered segments; bad_segment is the container's index
-__global__ __launch_bounds__(kScan) void seg_close_kernel(CloseArgs a)
-{
-    __shared__ unsigned long long s_bad;
-    const uint32_t tid = threadIdx.x;
-    if (tid == 0) s_bad = kNoSeg;
-    __syncthreads();
-    const int32_t top = (int32_t)a.ctl[0];
-    if (top == 0) {
-        // the lowest segment that failed, decoded cleanly to another length than its cut, or to
-        // that length with another checksum (crc[i] is written exactly for those that reach it)
-        uint64_t bad = kNoSeg;
-        for (uint64_t i = tid; i < a.count && bad == kNoSeg; i += kScan)
-            if (a.seg_status[i] != 0 || a.out_lens[i] != a.out_caps[i] || (a.crc && a.crc[i] != a.want_crc[i]))
-                bad = i;
-        if (bad != kNoSeg) atomicMin(&s_bad, (unsigned long long)bad);
-    }
-    __syncthreads();
-    if (tid != 0) return;
-    const uint64_t bad = s_bad;
-    int32_t st = top;
-    uint64_t len = top == HC_ERR_CAPACITY ? a.length : 0;
-    if (top == 0) {
-        if (bad != kNoSeg) {
-            st = a.seg_status[bad];
-            // 64: it wanted more room than its cut; 0: it decoded to fewer bytes, or to the wrong ones
-            if (st == 0 && a.out_lens[bad] == a.out_caps[bad]) st = HC_ERR_SEG_CHECK;
-            else if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
-        } else {
-            len = a.length;
-        }
-    }
-    *a.status = st;
-    *a.out_len = len;
-    if (a.bad_segment) *a.bad_segment = bad == kNoSeg ? kNoSeg : a.k0 + bad;
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -577,79 +283,17 @@ int seg_compress_host(const uint8_t *in, uint64_t in_len, uint32_t flags, uint64
     return HC_OK;
 }
 
-// the workspace of a range inside raw_len of a container whose info passed; enc_total: an upper
-// bound of the covered segments' encoded bytes (the adaptive batch workspace grows with it)
-DecWs dec_ws(void *work, const hc_seg_info_t &info, const Cuts &c, uint64_t offset, uint64_t length, bool whole,
-             uint64_t enc_total, DecPlan &p)
-{
-    p = dec_plan(c, offset, length, whole);
-    const uint64_t aw = ((info.flags & HC_FLAG_ADAPT) && p.cv.count)
-                            ? hc::adapt_decode_work_bound(enc_total, p.raw, (uint32_t)p.cv.count)
-                            : 0;
-    return carve_dec(work, p.cv.count, p.nslots, p.slot, aw, checked(info.flags));
-}
-
-// hc_seg_decompress_dev (whole: the range (0, raw_len) over every segment) and
-// hc_seg_decompress_range_dev; the host range call passes its compact upload's skip and span
-int decode_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, uint64_t offset, uint64_t length,
-               bool whole, uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status, uint64_t *bad_segment,
-               void *work, uint64_t work_bytes, void *stream, uint64_t skip, uint64_t enc_total)
-{
-    if (!in || !info || !out || !out_len || !status || !work) return HC_ERR_ARG;
-    if (!aligned16(in) || !aligned16(out) || !aligned16(work)) return HC_ERR_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Cuts c;
-    if (!info_ok(*info, in_len, c)) {
-        seg_reject_kernel<<<1, 1, 0, st>>>(out_len, status, bad_segment);
-        HC_CK(hipGetLastError());
-        return HC_OK;
-    }
-    if (whole) length = info->raw_len;
-    else if (!range_ok(info->raw_len, offset, length)) return HC_ERR_ARG;
-    if (c.n > kMaxSegs) return HC_ERR_ARG;
-    const bool adapt = (info->flags & HC_FLAG_ADAPT) != 0;
-    const bool check = checked(info->flags);
-    DecPlan p;
-    const DecWs w = dec_ws(work, *info, c, offset, length, whole, enc_total, p);
-    if (work_bytes < w.total) return HC_ERR_ARG;
-    const uint32_t count = (uint32_t)p.cv.count;
-
-    // one output base for the batch: whichever of out and the slots lies lower
-    uint8_t *base = (p.nslots && w.slots < out) ? w.slots : out;
-    const OpenArgs oa{in, in_len, skip, make_header(info->flags, info->raw_len, info->seg_bytes, info->width, c.n),
-                      c.n, c.full, c.last, offset, length, out_cap,
-                      p.cv.k0, p.cv.count, p.nslots, p.slot,
-                      (uint64_t)(out - base), p.nslots ? (uint64_t)(w.slots - base) : 0,
-                      w.in_offs, w.in_lens, w.out_offs, w.out_caps, w.out_lens,
-                      w.cp_src, w.cp_len, w.cp_dst, w.status, w.ctl, check};
-    seg_open_kernel<<<1, kScan, 0, st>>>(oa);
-    HC_CK(hipGetLastError());
-    if (count) {
-        Batch b{in, w.in_offs, w.in_lens, count, base, w.out_offs, w.out_caps, w.out_lens, w.status, 0};
-        if (adapt) HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
-        else HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
-        // segments that decoded cleanly to their cut's length, staged or in place (every covered
-        // one decodes whole, so its checksum is verifiable); none when the verdict is set
-        if (check)
-            HC_CK(hc::launch_crc32(base, w.out_offs, w.out_caps, count, w.crc, hc::CrcGate{w.ctl, w.status, w.out_lens}, st));
-    }
-    // the staged segments' covered parts to their places in out (empty copies when the verdict is set)
-    if (p.nslots) HC_CK(hc::launch_pack(w.slots, w.cp_src, w.cp_len, (uint32_t)p.nslots, out, w.cp_dst, st));
-    const CloseArgs ca{w.out_lens, w.out_caps, w.ctl, w.status, check ? w.crc : nullptr,
-                       check ? reinterpret_cast<const uint32_t *>(in + 48 + 8 * c.n) + p.cv.k0 : nullptr,
-                       p.cv.k0, p.cv.count, length, out_len, bad_segment, status};
-    seg_close_kernel<<<1, kScan, 0, st>>>(ca);
-    HC_CK(hipGetLastError());
-    return HC_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
-// Batches (hc_seg_*_batch_dev): many items per call over one concatenated segment array, so one
-// launch of each coder serves them all. The glue kernels above, per item: the item records reach
-// the device as kernel arguments, a chunk per launch (seg_items_kernel; the only launches that
-// grow with n_items), and live in the workspace from then on. Seal, open and close run one
-// workgroup per item, each with its own tiled scan; plan and gather run over the segments and
-// find their item by search and by the map that plan leaves. ctl is one word per item.
+// Items and the glue stages. A call codes one item or many (hc_seg_*_batch_dev) over one
+// concatenated segment array, so one launch of each coder serves them all. The item record
+// (EncItem, DecItem) is the one description of an item, and every stage is written once against
+// it. A batch's records reach the device as kernel arguments, a chunk per launch (seg_items_kernel;
+// the only launches that grow with n_items), and live in the workspace from then on (Many); a
+// single call is the one-item case (seg0, slot0 and every *_off 0, hs 0) with the record in the
+// stages' own kernel arguments (One): no seg_items_kernel launch, no record in memory, no search,
+// no map. Seal, open and close run one workgroup per item, each with its own tiled scan; plan and
+// gather run over the segments and, in a batch, find their item by search and by the map that
+// plan leaves. ctl is one word per item.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t kEncChunk = 32, kDecChunk = 16;  // items per descriptor launch (arguments: 4 KB at most)
 
@@ -661,8 +305,8 @@ struct EncItem {
     int64_t hs;  // the host-decided status
 };
 struct DecItem {
-    uint64_t in_off, in_len, skip;
-    uint64_t flags, raw_len, seg_bytes, width;  // header words 1 .. 4 (0: the magic, 5: n)
+    uint64_t in_off, in_len, skip;  // skip: what the covered segments' input offsets lose (a compact upload)
+    uint64_t flags, raw_len, seg_bytes, width;  // header words 1 .. 4 (0: the magic, 5: n), the caller's host copy
     uint64_t n, full, last, offset, length, out_cap;
     uint64_t k0, count, nslots, slot;
     uint64_t out_off, slot_off;  // from out, the slots
@@ -671,6 +315,55 @@ struct DecItem {
     int32_t hs;  // the host-decided status
 };
 static_assert(sizeof(EncItem) == 112 && sizeof(DecItem) == 176, "the work bounds of hcodec.h count these");
+
+// What the one item of a single call has by construction (enc_item, dec_item with seg0, slot0 and
+// slot_off 0 over a public item without offsets, after the host's checks), as constants: the
+// single calls' kernels carry no host-status branch and less offset arithmetic, and keep the
+// registers and the occupancy they had as kernels of their own (without this seg_seal_kernel<One>
+// has 7 waves for 8 and seg_open_kernel<One> 5 for 6; profiles/seg_unify_resource_usage.txt).
+__device__ inline EncItem alone(EncItem it)
+{
+    it.seg0 = it.in_off = it.slot_off = it.out_off = 0;
+    it.hs = 0;
+    return it;
+}
+__device__ inline DecItem alone(DecItem it)
+{
+    it.seg0 = it.slot0 = 0;  // (its three byte offsets stay values: folding them too doubles seg_open's scalar spills)
+    it.hs = 0;
+    return it;
+}
+
+// The item sources. at(i): item i's record; find(k): the item of segment k, the last one whose
+// seg0 is <= k (an item without segments shares its seg0 with the next one, which the search
+// passes); own / owner: the segment -> item map (encoder batches: plan writes it, gather reads it).
+template <class Item>
+struct One {
+    Item it;
+    __device__ Item at(uint32_t) const { return alone(it); }
+    __device__ uint32_t find(uint64_t) const { return 0; }
+    __device__ void own(uint64_t, uint32_t) const {}
+    __device__ uint32_t owner(uint64_t) const { return 0; }
+};
+template <class Item>
+struct Many {
+    const Item *items;
+    uint32_t n_items;
+    uint32_t *seg_item;  // (the decoder has none)
+    __device__ const Item &at(uint32_t i) const { return items[i]; }
+    __device__ uint32_t find(uint64_t k) const
+    {
+        uint32_t lo = 0, hi = n_items;  // items[lo].seg0 <= k < items[hi].seg0 (hi == n_items: the end)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (items[mid].seg0 <= k) lo = mid;
+            else hi = mid;
+        }
+        return lo;
+    }
+    __device__ void own(uint64_t k, uint32_t i) const { seg_item[k] = i; }
+    __device__ uint32_t owner(uint64_t k) const { return seg_item[k]; }
+};
 
 template <class Item, uint32_t N>
 struct ItemChunk {
@@ -735,60 +428,49 @@ EncBatchWs carve_enc_batch(void *work, uint64_t n_items, uint64_t n, uint64_t sl
     return w;
 }
 
-struct PlanBatchArgs {
-    const EncItem *items;
-    uint32_t n_items;
+// what the encoder's stages share: the arrays over all n segments of the call, and its outputs
+struct EncCall {
     uint64_t n;
-    uint64_t *in_offs, *in_lens, *widths, *out_offs, *out_caps, *out_lens;
-    int32_t *status;
-    uint32_t *seg_item;
+    uint64_t *in_offs, *in_lens, *widths, *slot_offs, *slot_caps, *enc_lens, *dst_offs;
+    int32_t *seg_status;
+    const uint32_t *crc;  // null: unchecked containers
+    uint64_t *ctl;        // [i] 1: item i is sealed, the gather may copy
+    const uint8_t *slots;
+    uint8_t *out;
+    uint64_t *out_lens;  // per item
+    int32_t *status;     // per item
+    uint64_t magic, flags, seg_bytes;  // header words 0, 1 and 3
 };
 
-// seg_plan_kernel over the concatenated segments: segment k belongs to the last item whose seg0
-// is <= k (an item without segments shares its seg0 with the next one, which the search passes)
-__global__ __launch_bounds__(256) void seg_plan_batch_kernel(PlanBatchArgs a)
+// segment k's input range and its output slot (all in closed form: only an item's last segment differs)
+template <class Src>
+__global__ __launch_bounds__(256) void seg_plan_kernel(Src items, EncCall a)
 {
     const uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= a.n) return;
-    uint32_t lo = 0, hi = a.n_items;  // items[lo].seg0 <= k < items[hi].seg0 (hi == n_items: the end)
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (a.items[mid].seg0 <= k) lo = mid;
-        else hi = mid;
-    }
-    const EncItem &it = a.items[lo];
+    const uint32_t item = items.find(k);
+    const EncItem &it = items.at(item);
     const uint64_t j = k - it.seg0;
     const bool tail = j == it.n - 1;
     a.in_offs[k] = it.in_off + j * it.full;
     a.in_lens[k] = tail ? it.last : it.full;
     a.widths[k] = it.width;
-    a.out_offs[k] = it.slot_off + j * it.slot_full;
-    a.out_caps[k] = tail ? it.cap_last : it.cap_full;
-    a.out_lens[k] = 0;
-    a.status[k] = HC_ERR_DEVICE;  // every segment is coded by exactly one launch, which overwrites this
-    a.seg_item[k] = lo;
+    a.slot_offs[k] = it.slot_off + j * it.slot_full;
+    a.slot_caps[k] = tail ? it.cap_last : it.cap_full;
+    a.enc_lens[k] = 0;
+    a.seg_status[k] = HC_ERR_DEVICE;  // every segment is coded by exactly one launch, which overwrites this
+    items.own(k, item);
 }
 
-struct SealBatchArgs {
-    const EncItem *items;
-    const uint64_t *enc_lens;
-    const int32_t *seg_status;
-    const uint32_t *crc;  // null: unchecked containers
-    uint64_t *dst_offs, *ctl;
-    uint8_t *out;
-    uint64_t *out_lens;
-    int32_t *status;
-    uint64_t magic, flags, seg_bytes;  // header words 0, 1 and 3
-};
-
-// seg_seal_kernel for item blockIdx.x: its segments' places from out (dst_offs), its verdict, its
-// header and index at out + out_off
-__global__ __launch_bounds__(kScan) void seg_seal_batch_kernel(SealBatchArgs a)
+// item blockIdx.x: its segments' places from out (dst_offs), its verdict, its header and index at
+// out + out_off
+template <class Src>
+__global__ __launch_bounds__(kScan) void seg_seal_kernel(Src items, EncCall a)
 {
     __shared__ uint64_t part[kScan / 64];
     __shared__ unsigned long long s_bad, s_end;
     const uint32_t tid = threadIdx.x, item = blockIdx.x;
-    const EncItem it = a.items[item];
+    const EncItem it = items.at(item);
     if (it.hs != 0) {  // decided on the host: no segment, no output byte
         if (tid == 0) {
             a.status[item] = (int32_t)it.hs;
@@ -843,20 +525,21 @@ __global__ __launch_bounds__(kScan) void seg_seal_batch_kernel(SealBatchArgs a)
         for (uint64_t k = tid; k < it.n; k += kScan) o32[12 + 2 * it.n + k] = crc[k];
 }
 
-// seg_gather_kernel over the concatenated segments: dst_offs count from out, and a segment is its
-// item's last one when it ends the item's run
-__global__ __launch_bounds__(256) void seg_gather_batch_kernel(const uint8_t *slots, const uint64_t *slot_offs,
-                                                               const uint64_t *enc_lens, const uint64_t *dst_offs,
-                                                               const uint64_t *ctl, const uint32_t *seg_item,
-                                                               const EncItem *items, uint64_t n, uint8_t *out)
+// Slot k -> out + dst_offs[k] (dst_offs count from out), one workgroup per segment. Both ends are
+// 16-byte aligned, so whole 16-byte chunks per lane; the chunk that holds the stream's last bytes
+// goes out with its padding zeroed, except that of an item's last segment (a container ends with
+// its last byte: bytes).
+template <class Src>
+__global__ __launch_bounds__(256) void seg_gather_kernel(Src items, EncCall a)
 {
-    for (uint64_t k = blockIdx.x; k < n; k += gridDim.x) {
-        const uint32_t item = seg_item[k];
-        if (ctl[item] == 0) continue;  // not sealed: nothing is copied
-        const bool last = k == items[item].seg0 + items[item].n - 1;
-        const uint64_t len = enc_lens[k];
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(slots + slot_offs[k]);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(out + dst_offs[k]);
+    for (uint64_t k = blockIdx.x; k < a.n; k += gridDim.x) {
+        const uint32_t item = items.owner(k);
+        if (a.ctl[item] == 0) continue;  // not sealed: nothing is copied
+        const EncItem &it = items.at(item);
+        const bool last = k == it.seg0 + it.n - 1;
+        const uint64_t len = a.enc_lens[k];
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(a.slots + a.slot_offs[k]);
+        u32x4 *dst = reinterpret_cast<u32x4 *>(a.out + a.dst_offs[k]);
         const uint64_t chunks = len / 16;
         for (uint64_t c = threadIdx.x; c < chunks; c += 256) dst[c] = src[c];
         const uint32_t rem = (uint32_t)(len & 15u);
@@ -906,22 +589,67 @@ EncBatchWs enc_batch_ws(void *work, uint32_t n_items, const EncTotals &t, int us
     return carve_enc_batch(work, n_items, t.n, t.slot_bytes, aw, check);
 }
 
+// the record of one input: hs its host_status; p (hs 0 alone) its plan; seg0 and slot_off where
+// its segments and their slots start
+EncItem enc_item(const hc_seg_enc_item_t &h, int hs, const EncPlan &p, int use_adapt, uint64_t seg0, uint64_t slot_off)
+{
+    EncItem r;
+    memset(&r, 0, sizeof(r));
+    r.seg0 = seg0;
+    r.hs = hs;
+    if (hs) return r;
+    return EncItem{seg0, p.c.n, p.c.full, p.c.last, p.slot_full, p.cap_full, p.cap_last,
+                   use_adapt ? h.width : 0, h.in_off, slot_off, h.out_off, h.out_cap, h.in_len, 0};
+}
+
+// The encoder's launches over the n_items records of `items`, whose n_segs segments fill the
+// arrays of s; ctl: a word per item. seg_bytes: the size in use, never 0.
+template <class Src>
+int encode_launch(const Src &items, uint32_t n_items, uint64_t n_segs, const EncWs &s, uint64_t *ctl,
+                  const uint8_t *in, uint8_t *out, uint32_t flags, uint64_t seg_bytes, uint64_t *out_lens,
+                  int32_t *status, hipStream_t st)
+{
+    const uint32_t n = (uint32_t)n_segs;
+    const bool check = checked(flags);
+    const EncCall ec{n_segs, s.in_offs, s.in_lens, s.widths, s.out_offs, s.out_caps, s.out_lens, s.dst_offs,
+                     s.status, check ? s.crc : nullptr, ctl, s.slots, out, out_lens, status,
+                     get64(kMagic), flags & 0xFFFFu, seg_bytes};  // byte 8 the flags, byte 9 the check kind
+    if (n) {
+        seg_plan_kernel<<<(n + 255) / 256, 256, 0, st>>>(items, ec);
+        HC_CK(hipGetLastError());
+        Batch b{in ? in : out, s.in_offs, s.in_lens, n, s.slots, s.out_offs, s.out_caps, s.out_lens, s.status,
+                flags & HC_FLAG_DIFF};
+        // the raw bytes of every cut, before the diff model (an empty input has one empty segment: crc 0)
+        if (check) HC_CK(hc::launch_crc32(b.in, s.in_offs, s.in_lens, n, s.crc, hc::CrcGate{nullptr, nullptr}, st));
+        if (flags & HC_FLAG_ADAPT) HC_CK(hc::adapt_encode_batch(b, s.widths, s.awork, s.awork_bytes, st));
+        else HC_CK(hc::launch_encode(b, (flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
+    }
+    seg_seal_kernel<<<n_items, kScan, 0, st>>>(items, ec);
+    if (n) seg_gather_kernel<<<n < 65536u ? n : 65536u, 256, 0, st>>>(items, ec);
+    HC_CK(hipGetLastError());
+    return HC_OK;
+}
+
 // --- decode ---
-struct DecBatchWs {
+// `count` covered segments and `nslots` staging slots over all items. What differs between the
+// calls comes in as byte counts: a single call has crc words for a checked container alone, one
+// 16-byte ctl region and no records; a batch has a crc word per segment (entry k of a checked
+// item's segment k alone is written and read), a ctl word and a record per item.
+struct DecWs {
     uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;
     int32_t *status;
-    uint32_t *crc;  // entry k of a checked item's segment k alone is written and read
+    uint32_t *crc;  // the decoded segments' CRC-32
     uint64_t *ctl;  // [i] item i's container-level status (0, HC_ERR_SEG_HEADER, HC_ERR_CAPACITY, or hs)
     DecItem *items;
-    uint64_t *cp_src, *cp_len, *cp_dst;
+    uint64_t *cp_src, *cp_len, *cp_dst;  // slot s: cp_len[s] bytes from slots + cp_src[s] to out + cp_dst[s]
     uint8_t *slots;
     void *awork;
     uint64_t awork_bytes, total;
 };
-DecBatchWs carve_dec_batch(void *work, uint64_t n_items, uint64_t count, uint64_t nslots, uint64_t slot_bytes,
-                           uint64_t awork_bytes)
+DecWs carve_dec(void *work, uint64_t count, uint64_t nslots, uint64_t slot_bytes, uint64_t awork_bytes,
+                uint64_t crc_bytes, uint64_t ctl_bytes, uint64_t n_records)
 {
-    DecBatchWs w;
+    DecWs w;
     uint8_t *p = static_cast<uint8_t *>(work);
     uint64_t o = 0;
     auto take = [&](uint64_t bytes) {
@@ -935,9 +663,9 @@ DecBatchWs carve_dec_batch(void *work, uint64_t n_items, uint64_t count, uint64_
     w.out_caps = reinterpret_cast<uint64_t *>(take(8 * count));
     w.out_lens = reinterpret_cast<uint64_t *>(take(8 * count));
     w.status = reinterpret_cast<int32_t *>(take(4 * count));
-    w.crc = reinterpret_cast<uint32_t *>(take(4 * count));
-    w.ctl = reinterpret_cast<uint64_t *>(take(8 * n_items));
-    w.items = reinterpret_cast<DecItem *>(take(sizeof(DecItem) * n_items));
+    w.crc = reinterpret_cast<uint32_t *>(take(crc_bytes));
+    w.ctl = reinterpret_cast<uint64_t *>(take(ctl_bytes));
+    w.items = reinterpret_cast<DecItem *>(take(sizeof(DecItem) * n_records));
     w.cp_src = reinterpret_cast<uint64_t *>(take(8 * nslots));
     w.cp_len = reinterpret_cast<uint64_t *>(take(8 * nslots));
     w.cp_dst = reinterpret_cast<uint64_t *>(take(8 * nslots));
@@ -948,26 +676,36 @@ DecBatchWs carve_dec_batch(void *work, uint64_t n_items, uint64_t count, uint64_
     return w;
 }
 
-struct OpenBatchArgs {
+// what the decoder's stages share: the arrays over all covered segments and all staging slots of
+// the call, and its outputs
+struct DecCall {
     const uint8_t *in;
-    const DecItem *items;
     uint64_t magic;          // header word 0
-    uint64_t out_d, slot_d;  // out and the slots from the batch's output base
-    uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;
+    uint64_t out_d, slot_d;  // out and the slots from the call's output base
+    uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *seg_out_lens;
     uint64_t *cp_src, *cp_len, *cp_dst;
-    int32_t *status;
-    uint64_t *ctl;
+    int32_t *seg_status;
+    const uint32_t *crc;  // of the decoded bytes (checked items' entries alone)
+    uint64_t *ctl;        // [i] item i's container-level status
+    uint64_t *out_lens, *bad_segments;  // per item (bad_segments: or null)
+    int32_t *status;                    // per item
 };
 
-// seg_open_kernel for item blockIdx.x: its header and index, its covered segments' entries from
-// seg0 on (input offsets from the call's `in`, outputs from the call's base), its copies from slot0
-// on (sources from the slots' start, destinations from `out`)
-__global__ __launch_bounds__(kScan) void seg_open_batch_kernel(OpenBatchArgs a)
+// Item blockIdx.x. The host has checked its copy of the header against in_len (48 + 8 n <= in_len
+// among the rest; 12 n in a checked container, whose crc words follow the lengths); here the
+// device bytes must equal that copy, and the index must tile [align16(48 + 8 n or 12 n), in_len)
+// exactly, whatever the range. enc_len entries are untrusted: the offsets add with saturation and
+// every range is compared by subtraction, so a forged length cannot wrap into a valid offset.
+// Segment arrays for the covered segments only (entry seg0 + k - k0; input offsets from the call's
+// `in`, outputs from the call's base), and the staged ones' copies from slot0 on (sources from the
+// slots' start, destinations from `out`).
+template <class Src>
+__global__ __launch_bounds__(kScan) void seg_open_kernel(Src items, DecCall a)
 {
     __shared__ uint64_t part[kScan / 64];
     __shared__ uint32_t s_err;
     const uint32_t tid = threadIdx.x, item = blockIdx.x;
-    const DecItem it = a.items[item];
+    const DecItem it = items.at(item);
     if (it.hs != 0) {  // decided on the host: no segment (count and nslots are 0), no output byte
         if (tid == 0) a.ctl[item] = (uint64_t)it.hs;
         return;
@@ -1006,8 +744,8 @@ __global__ __launch_bounds__(kScan) void seg_open_batch_kernel(OpenBatchArgs a)
             a.in_offs[e_i] = it.in_off + off - it.skip;  // (a wrapped value is never read: err zeroes in_lens)
             a.in_lens[e_i] = len;
             a.out_caps[e_i] = cap;
-            a.out_lens[e_i] = 0;
-            a.status[e_i] = HC_ERR_DEVICE;  // overwritten by the launch that owns the segment
+            a.seg_out_lens[e_i] = 0;
+            a.seg_status[e_i] = HC_ERR_DEVICE;  // overwritten by the launch that owns the segment
             if (all_staged || lo != b || hi != e) {
                 const uint64_t s = all_staged ? i : (i == 0 ? 0 : tail_slot);
                 a.out_offs[e_i] = a.slot_d + it.slot_off + s * it.slot;
@@ -1031,24 +769,15 @@ __global__ __launch_bounds__(kScan) void seg_open_batch_kernel(OpenBatchArgs a)
     for (uint64_t s = tid; s < it.nslots; s += kScan) cp_len[s] = 0;
 }
 
-struct CloseBatchArgs {
-    const uint8_t *in;
-    const DecItem *items;
-    const uint64_t *seg_out_lens, *seg_out_caps, *ctl;
-    const int32_t *seg_status;
-    const uint32_t *crc;
-    uint64_t *out_lens, *bad_segments;
-    int32_t *status;
-};
-
-// seg_close_kernel for item blockIdx.x
-__global__ __launch_bounds__(kScan) void seg_close_batch_kernel(CloseBatchArgs a)
+// item blockIdx.x: the verdict over its covered segments; bad_segment is the container's index
+template <class Src>
+__global__ __launch_bounds__(kScan) void seg_close_kernel(Src items, DecCall a)
 {
     __shared__ unsigned long long s_bad;
     const uint32_t tid = threadIdx.x, item = blockIdx.x;
-    const DecItem &it = a.items[item];
+    const DecItem &it = items.at(item);
     const uint64_t seg0 = it.seg0, count = it.count, k0 = it.k0, length = it.length;
-    const uint64_t *out_lens = a.seg_out_lens + seg0, *out_caps = a.seg_out_caps + seg0;
+    const uint64_t *out_lens = a.seg_out_lens + seg0, *out_caps = a.out_caps + seg0;
     const int32_t *seg_status = a.seg_status + seg0;
     // checked containers: the decoded bytes' crc, and the index's from k0
     const uint32_t *crc = it.check ? a.crc + seg0 : nullptr;
@@ -1057,6 +786,8 @@ __global__ __launch_bounds__(kScan) void seg_close_batch_kernel(CloseBatchArgs a
     __syncthreads();
     const int32_t top = (int32_t)a.ctl[item];
     if (top == 0) {
+        // the lowest segment that failed, decoded cleanly to another length than its cut, or to
+        // that length with another checksum (crc[i] is written exactly for those that reach it)
         uint64_t bad = kNoSeg;
         for (uint64_t i = tid; i < count && bad == kNoSeg; i += kScan)
             if (seg_status[i] != 0 || out_lens[i] != out_caps[i] || (crc && crc[i] != want_crc[i])) bad = i;
@@ -1085,7 +816,8 @@ __global__ __launch_bounds__(kScan) void seg_close_batch_kernel(CloseBatchArgs a
 // One decoder item on the host: its status when the host decides it (0: none), else its cuts, its
 // range (whole: (0, raw_len)) and its sizes. The segment arrays hold the items in four groups, so
 // that each launch covers one run of entries: plain unchecked, plain checked, adaptive checked,
-// adaptive unchecked (FGK the first two, adaptive the last two, CRC the middle two).
+// adaptive unchecked (FGK the first two, adaptive the last two, CRC the middle two). A single
+// call's item is the one non-empty group, from entry 0 on.
 struct DecOne {
     int hs;
     Cuts c;
@@ -1148,11 +880,33 @@ bool dec_totals(const hc_seg_dec_item_t *items, uint32_t n_items, const uint64_t
     }
     return true;
 }
-DecBatchWs dec_batch_ws(void *work, uint32_t n_items, const DecTotals &t)
+// single: the one-item call's layout (n_items 1)
+DecWs dec_ws(void *work, bool single, uint32_t n_items, const DecTotals &t)
 {
     const uint64_t aw = t.a_count ? hc::adapt_decode_work_bound(t.a_enc, t.a_raw, (uint32_t)t.a_count) : 0;
-    return carve_dec_batch(work, n_items, t.count, t.nslots, t.slot_bytes, aw);
+    if (single) return carve_dec(work, t.count, t.nslots, t.slot_bytes, aw, 4 * (t.seg[1] + t.seg[2]), 16, 0);
+    return carve_dec(work, t.count, t.nslots, t.slot_bytes, aw, 4 * t.count, 8ull * n_items, n_items);
 }
+
+// the record of one item: skip what its compact upload leaves out; seg0, slot0 and slot_off where
+// its entries of the segment arrays, of the copy arrays, and its slots start
+DecItem dec_item(const hc_seg_dec_item_t &h, const DecOne &d, uint64_t skip, uint64_t seg0, uint64_t slot0,
+                 uint64_t slot_off)
+{
+    DecItem r;
+    memset(&r, 0, sizeof(r));
+    r.hs = d.hs;
+    if (d.hs) return r;
+    return DecItem{h.in_off, h.in_len, skip,
+                   h.info.flags & 0xFFFFu, h.info.raw_len, h.info.seg_bytes, h.info.width,
+                   d.c.n, d.c.full, d.c.last, d.offset, d.length, h.out_cap,
+                   d.p.cv.k0, d.p.cv.count, d.p.nslots, d.p.slot,
+                   h.out_off, slot_off, seg0, slot0, d.check ? 1u : 0u, 0};
+}
+
+template <class Src>
+int decode_launch(const Src &items, uint32_t n_items, const DecTotals &t, const DecWs &w, const uint8_t *in, uint8_t *out,
+                  uint64_t *out_lens, int32_t *status, uint64_t *bad_segments, hipStream_t st);
 
 // hc_seg_decompress_batch_dev; the host batch call passes its compact uploads' skips and spans
 int decode_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_dec_item_t *items, uint32_t n_items,
@@ -1166,42 +920,42 @@ int decode_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_dec_item_t *i
         if ((items[i].in_off | items[i].out_off) & 15u) return HC_ERR_ARG;
     DecTotals t;
     if (!dec_totals(items, n_items, enc_totals, t)) return HC_ERR_ARG;
-    const DecBatchWs w = dec_batch_ws(work, n_items, t);
+    const DecWs w = dec_ws(work, false, n_items, t);
     if (work_bytes < w.total) return HC_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
 
     // the groups' first entries, and the records
     uint64_t next[4] = {0, t.seg[0], t.seg[0] + t.seg[1], t.seg[0] + t.seg[1] + t.seg[2]};
-    const uint64_t n_fgk = next[2], crc0 = next[1], n_crc = t.seg[1] + t.seg[2];
     uint64_t slot0 = 0, slot_off = 0;
     ItemFeed<DecItem, kDecChunk> feed(w.items, st);
     for (uint32_t i = 0; i < n_items; ++i) {
-        const hc_seg_dec_item_t &h = items[i];
-        const DecOne d = dec_one(h);
-        DecItem r;
-        memset(&r, 0, sizeof(r));
-        r.hs = d.hs;
-        if (!d.hs) {
-            r = DecItem{h.in_off, h.in_len, skips ? skips[i] : 0,
-                        h.info.flags & 0xFFFFu, h.info.raw_len, h.info.seg_bytes, h.info.width,
-                        d.c.n, d.c.full, d.c.last, d.offset, d.length, h.out_cap,
-                        d.p.cv.k0, d.p.cv.count, d.p.nslots, d.p.slot,
-                        h.out_off, slot_off, next[d.group], slot0, d.check ? 1u : 0u, 0};
-            next[d.group] += d.p.cv.count;
-            slot0 += d.p.nslots;
-            slot_off += d.p.nslots * d.p.slot;
-        }
-        feed.push(r);
+        const DecOne d = dec_one(items[i]);
+        feed.push(dec_item(items[i], d, skips ? skips[i] : 0, next[d.group], slot0, slot_off));
+        if (d.hs) continue;
+        next[d.group] += d.p.cv.count;
+        slot0 += d.p.nslots;
+        slot_off += d.p.nslots * d.p.slot;
     }
     feed.flush();
     HC_CK(hipGetLastError());
+    return decode_launch(Many<DecItem>{w.items, n_items, nullptr}, n_items, t, w, in, out, out_lens, status, bad_segments,
+                         st);
+}
 
+// The decoder's launches over the n_items records of `items`, whose covered segments fill the
+// arrays of w group by group (t): open, the coder or coders, CRC, pack, close.
+template <class Src>
+int decode_launch(const Src &items, uint32_t n_items, const DecTotals &t, const DecWs &w, const uint8_t *in, uint8_t *out,
+                  uint64_t *out_lens, int32_t *status, uint64_t *bad_segments, hipStream_t st)
+{
+    // the groups' runs of entries: FGK [0, n_fgk), adaptive the rest, CRC [crc0, crc0 + n_crc)
+    const uint64_t n_fgk = t.seg[0] + t.seg[1], crc0 = t.seg[0], n_crc = t.seg[1] + t.seg[2];
     // one output base for the call: whichever of out and the slots lies lower
     uint8_t *base = (t.nslots && w.slots < out) ? w.slots : out;
-    const OpenBatchArgs oa{in, w.items, get64(kMagic), (uint64_t)(out - base), t.nslots ? (uint64_t)(w.slots - base) : 0,
-                           w.in_offs, w.in_lens, w.out_offs, w.out_caps, w.out_lens,
-                           w.cp_src, w.cp_len, w.cp_dst, w.status, w.ctl};
-    seg_open_batch_kernel<<<n_items, kScan, 0, st>>>(oa);
+    const DecCall dc{in, get64(kMagic), (uint64_t)(out - base), t.nslots ? (uint64_t)(w.slots - base) : 0,
+                     w.in_offs, w.in_lens, w.out_offs, w.out_caps, w.out_lens,
+                     w.cp_src, w.cp_len, w.cp_dst, w.status, w.crc, w.ctl, out_lens, bad_segments, status};
+    seg_open_kernel<<<n_items, kScan, 0, st>>>(items, dc);
     HC_CK(hipGetLastError());
     if (n_fgk) {
         Batch b{in, w.in_offs, w.in_lens, (uint32_t)n_fgk, base, w.out_offs, w.out_caps, w.out_lens, w.status, 0};
@@ -1212,17 +966,60 @@ int decode_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_dec_item_t *i
                 w.out_caps + n_fgk, w.out_lens + n_fgk, w.status + n_fgk, 0};
         HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
     }
-    // the checked items' segments that decoded cleanly to their cut's length; an item whose verdict
-    // is set has empty inputs, which no coder answers with status 0, so the per-segment gate alone
+    // the checked items' segments that decoded cleanly to their cut's length, staged or in place
+    // (every covered one decodes whole, so its checksum is verifiable); an item whose verdict
+    // is set has empty inputs, which no coder answers with status 0, so the per-segment gate
     // keeps the launch away from it
     if (n_crc)
         HC_CK(hc::launch_crc32(base, w.out_offs + crc0, w.out_caps + crc0, n_crc, w.crc + crc0,
-                               hc::CrcGate{nullptr, w.status + crc0, w.out_lens + crc0}, st));
+                               hc::CrcGate{w.status + crc0, w.out_lens + crc0}, st));
+    // the staged segments' covered parts to their places in out (empty copies when the verdict is set)
     if (t.nslots) HC_CK(hc::launch_pack(w.slots, w.cp_src, w.cp_len, (uint32_t)t.nslots, out, w.cp_dst, st));
-    const CloseBatchArgs ca{in, w.items, w.out_lens, w.out_caps, w.ctl, w.status, w.crc, out_lens, bad_segments, status};
-    seg_close_batch_kernel<<<n_items, kScan, 0, st>>>(ca);
+    seg_close_kernel<<<n_items, kScan, 0, st>>>(items, dc);
     HC_CK(hipGetLastError());
     return HC_OK;
+}
+
+// The single calls' item: a range inside raw_len of a container whose info passed info_ok (whole:
+// the range (0, raw_len) over every segment), and its workspace; enc_total as in dec_totals.
+hc_seg_dec_item_t single_item(const hc_seg_info_t &info, uint64_t in_len, uint64_t offset, uint64_t length, bool whole,
+                              uint64_t out_cap)
+{
+    return hc_seg_dec_item_t{0, in_len, info, whole ? 0 : offset, whole ? HC_SEG_WHOLE : length, 0, out_cap};
+}
+uint64_t single_work_bound(const hc_seg_info_t &info, uint64_t in_len, uint64_t offset, uint64_t length, bool whole,
+                           uint64_t enc_total)
+{
+    const hc_seg_dec_item_t h = single_item(info, in_len, offset, length, whole, 0);
+    DecTotals t;
+    if (!dec_totals(&h, 1, &enc_total, t)) return 0;
+    return dec_ws(nullptr, true, 1, t).total;
+}
+
+// hc_seg_decompress_dev (whole: the range (0, raw_len) over every segment) and
+// hc_seg_decompress_range_dev; the host range call passes its compact upload's skip and span
+int decode_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, uint64_t offset, uint64_t length,
+               bool whole, uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status, uint64_t *bad_segment,
+               void *work, uint64_t work_bytes, void *stream, uint64_t skip, uint64_t enc_total)
+{
+    if (!in || !info || !out || !out_len || !status || !work) return HC_ERR_ARG;
+    if (!aligned16(in) || !aligned16(out) || !aligned16(work)) return HC_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Cuts c;
+    if (!info_ok(*info, in_len, c)) {
+        seg_reject_kernel<<<1, 1, 0, st>>>(out_len, status, bad_segment);
+        HC_CK(hipGetLastError());
+        return HC_OK;
+    }
+    if (!whole && !range_ok(info->raw_len, offset, length)) return HC_ERR_ARG;
+    if (c.n > kMaxSegs) return HC_ERR_ARG;
+    const hc_seg_dec_item_t h = single_item(*info, in_len, offset, length, whole, out_cap);
+    DecTotals t;
+    if (!dec_totals(&h, 1, &enc_total, t)) return HC_ERR_ARG;
+    const DecWs w = dec_ws(work, true, 1, t);
+    if (work_bytes < w.total) return HC_ERR_ARG;
+    const One<DecItem> item{dec_item(h, dec_one(h), skip, 0, 0, 0)};
+    return decode_launch(item, 1, t, w, in, out, out_len, status, bad_segment, st);
 }
 
 // the host batch calls' sub-batch limit, as hc_pipe.hip reads it
@@ -1290,29 +1087,11 @@ int hc_seg_compress_dev(const uint8_t *in, uint64_t in_len, uint32_t flags, uint
     if (!seg_bytes) seg_bytes = HC_SEG_DEFAULT_BYTES;
     EncPlan p;
     if (!enc_plan(in_len, seg_bytes, use_adapt, width, p)) return HC_ERR_ARG;
-    const bool check = checked(flags);
-    const EncWs w = carve_enc(work, p.c.n, p.slot_bytes, p.awork_bytes, check);
+    const EncWs w = carve_enc(work, p.c.n, p.slot_bytes, p.awork_bytes, checked(flags));
     if (work_bytes < w.total) return HC_ERR_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t n = (uint32_t)p.c.n;
-
-    const PlanArgs pa{w.in_offs, w.in_lens, w.widths, w.out_offs, w.out_caps, w.out_lens, w.status,
-                      p.c.n, p.c.full, p.c.last, p.slot_full, p.cap_full, p.cap_last, use_adapt ? width : 0};
-    seg_plan_kernel<<<(n + 255) / 256, 256, 0, st>>>(pa);
-    HC_CK(hipGetLastError());
-    Batch b{in ? in : out, w.in_offs, w.in_lens, n, w.slots, w.out_offs, w.out_caps, w.out_lens, w.status,
-            flags & HC_FLAG_DIFF};
-    // the raw bytes of every cut, before the diff model (an empty input has one empty segment: crc 0)
-    if (check) HC_CK(hc::launch_crc32(b.in, w.in_offs, w.in_lens, n, w.crc, hc::CrcGate{nullptr, nullptr, nullptr}, st));
-    if (use_adapt) HC_CK(hc::adapt_encode_batch(b, w.widths, w.awork, w.awork_bytes, st));
-    else HC_CK(hc::launch_encode(b, (flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
-    const SealArgs sa{w.out_lens, w.status, check ? w.crc : nullptr, w.dst_offs, w.ctl, p.c.n, out, out_cap, out_len, status,
-                      make_header(flags, in_len, seg_bytes, use_adapt ? width : 0, p.c.n)};
-    seg_seal_kernel<<<1, kScan, 0, st>>>(sa);
-    seg_gather_kernel<<<n < 65536u ? n : 65536u, 256, 0, st>>>(w.slots, w.out_offs, w.out_lens, w.dst_offs, w.ctl,
-                                                               p.c.n, out);
-    HC_CK(hipGetLastError());
-    return HC_OK;
+    const One<EncItem> item{enc_item(hc_seg_enc_item_t{0, in_len, width, 0, out_cap}, 0, p, use_adapt, 0, 0)};
+    return encode_launch(item, 1, p.c.n, w, w.ctl, in, out, flags, seg_bytes, out_len, status,
+                         static_cast<hipStream_t>(stream));
 }
 
 uint64_t hc_seg_decompress_work_bound(const hc_seg_info_t *info, uint64_t in_len)
@@ -1320,8 +1099,7 @@ uint64_t hc_seg_decompress_work_bound(const hc_seg_info_t *info, uint64_t in_len
     if (!info) return 0;
     Cuts c;
     if (!info_ok(*info, in_len, c) || c.n > kMaxSegs) return 16;  // rejected without a workspace
-    DecPlan p;
-    return dec_ws(nullptr, *info, c, 0, info->raw_len, true, in_len, p).total;
+    return single_work_bound(*info, in_len, 0, 0, true, in_len);
 }
 
 int hc_seg_decompress_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, uint8_t *out,
@@ -1382,8 +1160,7 @@ uint64_t hc_seg_decompress_range_work_bound(const hc_seg_info_t *info, uint64_t 
     Cuts c;
     if (!info_ok(*info, in_len, c) || c.n > kMaxSegs) return 16;  // rejected without a workspace
     if (!range_ok(info->raw_len, offset, length)) return 0;
-    DecPlan p;
-    return dec_ws(nullptr, *info, c, offset, length, false, in_len, p).total;
+    return single_work_bound(*info, in_len, offset, length, false, in_len);
 }
 
 int hc_seg_decompress_range_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, uint64_t offset,
@@ -1420,8 +1197,7 @@ int hc_seg_decompress_range(const uint8_t *in, uint64_t in_len, uint64_t offset,
     (void)fail(HC_OK, 0);  // (what a HIP error below leaves behind)
     // the compact upload: header and index [0, idx), then the span; in_len stays the container's
     const uint64_t span = s1 - s0;
-    DecPlan p;
-    const uint64_t wb = dec_ws(nullptr, info, c, offset, length, false, span, p).total;
+    const uint64_t wb = single_work_bound(info, in_len, offset, length, false, span);
     hipStream_t st = nullptr;
     DevBuf din, dout, work, meta;
     HC_CK(din.alloc(idx + span + 16));
@@ -1476,49 +1252,23 @@ int hc_seg_compress_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_enc_
     const EncBatchWs w = enc_batch_ws(work, n_items, t, use_adapt, check);
     if (work_bytes < w.total) return HC_ERR_ARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint32_t n = (uint32_t)t.n;
 
     uint64_t seg0 = 0, slot_off = 0;
     ItemFeed<EncItem, kEncChunk> feed(w.items, st);
     for (uint32_t i = 0; i < n_items; ++i) {
         const hc_seg_enc_item_t &h = items[i];
-        EncItem r;
-        memset(&r, 0, sizeof(r));
-        r.seg0 = seg0;
-        r.hs = host_status(h.in_len, use_adapt, h.width);
-        if (!r.hs) {
-            EncPlan p;
-            (void)enc_plan(h.in_len, seg_bytes, use_adapt, h.width, p);
-            r = EncItem{seg0, p.c.n, p.c.full, p.c.last, p.slot_full, p.cap_full, p.cap_last,
-                        use_adapt ? h.width : 0, h.in_off, slot_off, h.out_off, h.out_cap, h.in_len, 0};
-            seg0 += p.c.n;
-            slot_off += p.slot_bytes;
-        }
-        feed.push(r);
+        const int hs = host_status(h.in_len, use_adapt, h.width);
+        EncPlan p{};
+        if (!hs) (void)enc_plan(h.in_len, seg_bytes, use_adapt, h.width, p);
+        feed.push(enc_item(h, hs, p, use_adapt, seg0, slot_off));
+        if (hs) continue;
+        seg0 += p.c.n;
+        slot_off += p.slot_bytes;
     }
     feed.flush();
     HC_CK(hipGetLastError());
-    const EncWs &s = w.s;
-    if (n) {
-        const PlanBatchArgs pa{w.items, n_items, t.n, s.in_offs, s.in_lens, s.widths, s.out_offs, s.out_caps,
-                               s.out_lens, s.status, w.seg_item};
-        seg_plan_batch_kernel<<<(n + 255) / 256, 256, 0, st>>>(pa);
-        HC_CK(hipGetLastError());
-        Batch b{in ? in : out, s.in_offs, s.in_lens, n, s.slots, s.out_offs, s.out_caps, s.out_lens, s.status,
-                flags & HC_FLAG_DIFF};
-        // the raw bytes of every cut, before the diff model (an empty input has one empty segment: crc 0)
-        if (check) HC_CK(hc::launch_crc32(b.in, s.in_offs, s.in_lens, n, s.crc, hc::CrcGate{nullptr, nullptr, nullptr}, st));
-        if (use_adapt) HC_CK(hc::adapt_encode_batch(b, s.widths, s.awork, s.awork_bytes, st));
-        else HC_CK(hc::launch_encode(b, (flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
-    }
-    const SealBatchArgs sa{w.items, s.out_lens, s.status, check ? s.crc : nullptr, s.dst_offs, w.ctl, out, out_lens,
-                           status, get64(kMagic), flags & 0xFFFFu, seg_bytes};
-    seg_seal_batch_kernel<<<n_items, kScan, 0, st>>>(sa);
-    if (n)
-        seg_gather_batch_kernel<<<n < 65536u ? n : 65536u, 256, 0, st>>>(s.slots, s.out_offs, s.out_lens, s.dst_offs,
-                                                                         w.ctl, w.seg_item, w.items, t.n, out);
-    HC_CK(hipGetLastError());
-    return HC_OK;
+    return encode_launch(Many<EncItem>{w.items, n_items, w.seg_item}, n_items, t.n, w.s, w.ctl, in, out, flags, seg_bytes,
+                         out_lens, status, st);
 }
 
 uint64_t hc_seg_decompress_batch_work_bound(const hc_seg_dec_item_t *items, uint32_t n_items)
@@ -1526,7 +1276,7 @@ uint64_t hc_seg_decompress_batch_work_bound(const hc_seg_dec_item_t *items, uint
     if (!items && n_items) return 0;
     DecTotals t;
     if (!dec_totals(items, n_items, nullptr, t)) return 0;
-    return dec_batch_ws(nullptr, n_items, t).total;
+    return dec_ws(nullptr, false, n_items, t).total;
 }
 
 int hc_seg_decompress_batch_dev(const uint8_t *in, uint8_t *out, const hc_seg_dec_item_t *items, uint32_t n_items,
@@ -1697,7 +1447,7 @@ int hc_seg_decompress_host_batch(const uint8_t *const *in, const uint64_t *in_le
         const uint32_t m = (uint32_t)items.size();
         DecTotals tot;
         if (!dec_totals(items.data(), m, spans.data(), tot)) return HC_ERR_ARG;
-        const uint64_t wb = dec_batch_ws(nullptr, m, tot).total;
+        const uint64_t wb = dec_ws(nullptr, false, m, tot).total;
         HC_CK(din.alloc(in_total));
         HC_CK(dout.alloc(out_total));
         HC_CK(work.alloc(wb));

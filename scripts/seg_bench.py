@@ -50,8 +50,7 @@ SIDE = 4096
 MODES = {"-m": (1, 0), "-a -m": (1, 1), "-a": (0, 1)}
 SIZES = (16384, 65536, 262144)
 GLUE = ("seg_plan_kernel", "seg_seal_kernel", "seg_gather_kernel", "seg_open_kernel", "seg_close_kernel",
-        "crc32_kernel", "pack_kernel", "seg_items_kernel", "seg_plan_batch_kernel", "seg_seal_batch_kernel",
-        "seg_gather_batch_kernel", "seg_open_batch_kernel", "seg_close_batch_kernel")
+        "crc32_kernel", "pack_kernel", "seg_items_kernel")
 BATCH_SIDE, BATCH_ITEM, BATCH_NS = 8192, 1 << 20, (4, 16, 64)
 
 
