@@ -230,6 +230,21 @@ static_assert(HC_ENC_PACK >= 1 && HC_ENC_PACK <= 16, "a step's symbols are the l
 #ifndef HC_ENC_HANDOFF_LEVEL
 #define HC_ENC_HANDOFF_LEVEL 0
 #endif
+// HC_ENC_MISS_RUN 1 (the path-cache kernel): after the symbol that ended a regular step is coded
+// alone, the symbols right behind it that the step read as uncached are coded alone too, up to
+// HC_ENC_MISS_RUN_MAX (1..15) of them, instead of starting a step that takes nothing (model:
+// tests/fgk_missrun_model.py; photo -c -m: 13 % of the steps took nothing, 5 % with the rule).
+// Measured (C5 encode, alternating pairs against the parent's 306.3 / 306.2 / 306.5 ms): as an
+// inner loop round the one call site of the miss path 316.1 / 316.2 / 316.1, as a loop that
+// takes a step or a run symbol per pass 318.8 / 318.9 / 318.7: the steps saved are fewer
+// instructions in the model and more time on the GPU. Off. DESIGN.md section 7.
+#ifndef HC_ENC_MISS_RUN
+#define HC_ENC_MISS_RUN 0
+#endif
+#ifndef HC_ENC_MISS_RUN_MAX
+#define HC_ENC_MISS_RUN_MAX 15
+#endif
+static_assert(HC_ENC_MISS_RUN_MAX >= 1 && HC_ENC_MISS_RUN_MAX <= 15, "a run lies inside one step's 16 read lanes");
 // decoder (narrow and wide layouts): HC_DEC_BATCH != 0: up to HC_DEC_PACK (4, 8, ... 24) codes
 // per step, packed by bit offset (one lane per code bit), from one read of the level tables at
 // every bit offset and one tentative commit (Dec::decode_batch; HC_DEC_BATCH 0: the one-symbol
@@ -321,6 +336,19 @@ constexpr uint32_t kBatchYield = HC_BATCH_YIELD;  // Dec::run: twice the symbols
 #define HC_WALK_LIGHT 64
 #endif
 constexpr uint32_t kWalkLight = HC_WALK_LIGHT;
+// HC_WALK_LEAN 1: walk()'s climb back to the known path carries only the level's own work: the
+// lane to write is a running 64-bit mask (no counter beside it, the level count read off it once
+// after the loop), the select writes its register in place, the bound is the mask running out (64
+// levels), the loop branches on the compare and the meeting lanes are formed once after it
+// (climb_to: 7 VALU + SALU a level where the compiled loop had 12). A climb of no level (the parent
+// is on the known path) keeps that path and updates it from the meeting lane up, without the shift
+// through ds_bpermute. In the path-cache encoders and the decoders (Fgk::kLean). 0: the loop as
+// before everywhere (the parent commit's assembly). Measured (C5, alternating pairs):
+// encode 306.30 / 306.17 / 306.45 -> 302.51 / 301.95 / 302.29 ms, decode 348.46 / 349.04 / 349.16
+// -> 340.81 / 343.49 / 343.66. Model: tests/fgk_walk_model.py.
+#ifndef HC_WALK_LEAN
+#define HC_WALK_LEAN 1
+#endif
 constexpr uint32_t kSymWords = 88;  // encoder: MNP-5 symbols of one 256-byte chunk, <= 342
                                     // (a byte emits 2 only at a run start that follows a run of
                                     // >= 3, so such bytes are >= 3 apart)
@@ -432,6 +460,61 @@ __device__ __forceinline__ uint32_t sel(uint64_t m, uint32_t t, uint32_t f)
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(f), "v"(t), "s"(m));
     return r;
 }
+// ballot(a == b) as an instruction of its own
+[[maybe_unused]] __device__ __forceinline__ uint64_t lanes_eq(uint32_t a, uint32_t b)
+{
+    uint64_t r;
+    asm("v_cmp_eq_u32_e64 %0, %1, %2" : "=s"(r) : "v"(a), "v"(b));
+    return r;
+}
+// walk()'s climb from position c (wave-uniform, in a VGPR) until it equals a lane of pv: the j-th
+// position passed goes to lane j of td, c := its parent. kWide 0: the parent is the low ten bits
+// of the 32-bit word at base + 4 c; 1: the 16-bit word at base + 2 c. lm starts as 1 and ends as
+// 1 << (positions passed); 0: 64 were passed and no lane of pv met (the caller reports the bug).
+// Written out because the compiler, given the same loop in C++ with the select in place ("+v"),
+// copies td and the mask into fresh registers and back every level (12 instructions a level, as
+// with the counter and the shift it had before); here a level is 7 (6 wide): address, [mask of
+// the parent field,] compare, branch, select into the mask's lane, mask shift, branch on its
+// carry-out. The read is waited for inside (lgkmcnt(0)); nothing else is in flight that matters.
+template <bool kWide>
+[[maybe_unused]] __device__ __forceinline__ void climb_to(uint32_t &c, uint32_t &td, uint64_t &lm, uint32_t pv, uint32_t base)
+{
+    uint32_t a;
+    if constexpr (kWide) {
+        asm volatile("s_branch 3f\n"
+                     "1:\n\t"
+                     "v_lshl_add_u32 %3, %0, 1, %5\n\t"
+                     "ds_read_u16 %0, %3\n\t"
+                     "s_waitcnt lgkmcnt(0)\n"
+                     "3:\n\t"
+                     "v_cmp_eq_u32_e32 vcc, %4, %0\n\t"
+                     "s_cbranch_vccnz 2f\n\t"
+                     "v_cndmask_b32_e64 %1, %1, %0, %2\n\t"
+                     "s_lshl_b64 %2, %2, 1\n\t"
+                     "s_cbranch_scc1 1b\n"
+                     "2:"
+                     : "+v"(c), "+v"(td), "+s"(lm), "=&v"(a)
+                     : "v"(pv), "s"(base)
+                     : "vcc", "scc", "memory");
+    } else {
+        asm volatile("s_branch 3f\n"
+                     "1:\n\t"
+                     "v_lshl_add_u32 %3, %0, 2, %5\n\t"
+                     "ds_read_b32 %0, %3\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\t"
+                     "v_and_b32_e32 %0, 0x3ff, %0\n"
+                     "3:\n\t"
+                     "v_cmp_eq_u32_e32 vcc, %4, %0\n\t"
+                     "s_cbranch_vccnz 2f\n\t"
+                     "v_cndmask_b32_e64 %1, %1, %0, %2\n\t"
+                     "s_lshl_b64 %2, %2, 1\n\t"
+                     "s_cbranch_scc1 1b\n"
+                     "2:"
+                     : "+v"(c), "+v"(td), "+s"(lm), "=&v"(a)
+                     : "v"(pv), "s"(base)
+                     : "vcc", "scc", "memory");
+    }
+}
 // A wave-uniform value held in a VGPR: hiding its uniformity from the compiler moves the
 // arithmetic on it from the (saturated) scalar unit to the vector ALUs. Branches on such
 // values go through ballot(), which is uniform again.
@@ -513,6 +596,10 @@ struct Fgk {
     static constexpr bool kHuge = kW == 2;  // 64-bit weights
     using Wt = WeightT<kW>;
     static constexpr Wt kInc = kWide ? 1u : 1024u;
+    // walk(): the lean climb (HC_WALK_LEAN) in the path-cache encoder and the decoder; the table-mode
+    // and the small-alphabet encoder keep the compiled loop (their assembly is the parent's): noise
+    // -c -m encode 203.8 / 204.9 -> 207.0 / 206.8 ms and grad 1.267 / 1.268 -> 1.272 / 1.276 with it
+    static constexpr bool kLean = HC_WALK_LEAN && (kDec || (!kTab && !kSmall));
 
     Tree<kW, kDec, kTab, kSmall> &T;
     uint32_t lane;
@@ -1009,24 +1096,48 @@ struct Fgk {
             // into lane n (a scalar bit mask), the parent read and a mask -- no hop through the
             // scalar unit (with the position in an SGPR the compiler spent ~6 VALU + 11 SALU per
             // level on copies, readfirstlane and the address)
-            uint32_t c = vreg(p), n = 0, td = kRoot;
-            uint64_t on;
-#pragma unroll 1
-            while ((on = ballot(pv == c)) == 0) {
-                td = sel(1ull << n, c, td);
-                if (++n >= 63) {  // a valid path is shorter (pv's kRoot lanes end every climb): a bug
+            if constexpr (kLean) {
+                uint32_t c = p, td = kRoot;
+                uint64_t lm = 1;  // the lane the next chased position goes to
+                climb_to<kWide>(c, td, lm, pv, kWide ? lds_off16(&T.up[0]) : lds_off(&T.wt[0]));
+                if (lm == 0) {  // 64 levels: a valid path is shorter (pv's kRoot lanes end every climb): a bug
                     bad = 1;
                     return;
                 }
-                c = kWide ? (uint32_t)T.up[c] : ((uint32_t)T.wt[c] & 1023u);
+                const uint64_t on = lanes_eq(pv, c);
+                uint32_t k;
+                if (lm == 1) {
+                    // met at once: pv from the meeting lane up is the rest of the path as it stands
+                    k = update_from(pv, ff1(on));
+                } else {
+                    const uint32_t n = (uint32_t)__builtin_ctzll(lm);
+                    const uint32_t src = lane - n + ff1(on);
+                    const uint32_t up = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src * 4), (int)pv);
+                    pv = lane < n ? td : (src < 64 ? up : kRoot);
+                    k = update_from(pv, 0);
+                }
+                if (k == 0xFFFFFFFFu) return;  // the root too
+                s = lane_read(pv, k);
+            } else {
+                uint32_t c = vreg(p), n = 0, td = kRoot;
+                uint64_t on;
+#pragma unroll 1
+                while ((on = ballot(pv == c)) == 0) {
+                    td = sel(1ull << n, c, td);
+                    if (++n >= 63) {  // a valid path is shorter (pv's kRoot lanes end every climb): a bug
+                        bad = 1;
+                        return;
+                    }
+                    c = kWide ? (uint32_t)T.up[c] : ((uint32_t)T.wt[c] & 1023u);
+                }
+                // lane j < n: chased; lane j >= n: pv's lane j - n + m (kRoot past its lane 63)
+                const uint32_t src = lane - n + ff1(on);
+                const uint32_t up = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src * 4), (int)pv);
+                pv = lane < n ? td : (src < 64 ? up : kRoot);
+                const uint32_t k = update_from(pv, 0);
+                if (k == 0xFFFFFFFFu) return;  // the root too
+                s = lane_read(pv, k);
             }
-            // lane j < n: chased; lane j >= n: pv's lane j - n + m (kRoot past its lane 63)
-            const uint32_t src = lane - n + ff1(on);
-            const uint32_t up = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src * 4), (int)pv);
-            pv = lane < n ? td : (src < 64 ? up : kRoot);
-            const uint32_t k = update_from(pv, 0);
-            if (k == 0xFFFFFFFFu) return;  // the root too
-            s = lane_read(pv, k);
         }
     }
 
@@ -1804,6 +1915,9 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
         const uint32_t scb = lds_off(fgk.scr32());
         constexpr uint64_t kL63 = 1ull << 63;
         uint32_t t = 0;
+#if HC_ENC_MISS_RUN
+        uint32_t stepmm = 0;  // the last step's mm: bit j: symbol j had no row when the step read it
+#endif
         // One regular step from symbol t on (the comment above). Returns the index in the step of
         // the symbol that ended it and is to be coded alone (kNone: the cap, the lanes or the pass
         // ended it), with t and sink.n moved past the symbols before it; sv, wh: lane j holds the
@@ -1828,6 +1942,9 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
             // the symbols without a row, within the cap and the pass; the first symbol not taken
             const uint32_t mm = (uint32_t)ballot(wh < 1024u) & ((1u << lim) - 1u);
             const uint32_t jmax = (uint32_t)__builtin_ctz(mm | (uint32_t)ballot(inc > 63u) | (1u << lim));
+#if HC_ENC_MISS_RUN
+            stepmm = mm;
+#endif
             lv = 0;
             if (jmax == 0) return 0;  // (a cached path is at most kInsertDepth lanes: the first symbol has no row)
             const uint32_t se = lane_read(inc, jmax - 1);  // the lanes of the symbols taken, <= 63
@@ -1916,6 +2033,48 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
         // small-alphabet steps (above) while the stream has seen <= 16 symbols; re-checked only
         // after a symbol coded alone (splits happen there), so a regular step pays nothing for it
         if constexpr (!kSmall) {
+#if HC_ENC_MISS_RUN
+            // (the path-cache kernel: one regular batch step per pass of this loop; behind the
+            // symbol coded alone, those the step read as uncached too are coded alone at once --
+            // a step from there would take nothing (jmax == 0) after three dependent LDS round
+            // trips. Only the count crosses the miss path; the run's symbols are looked up afresh,
+            // which is right whatever became of them meanwhile (one equal to a symbol just
+            // inserted is cached by now). mm ends at the step's cap and the pass's end, so does
+            // the run. One call site: the miss path stays inlined once. sink.n < 64 throughout:
+            // the step leaves room for the symbol that ends it, and push() packs at 64. Model:
+            // tests/fgk_missrun_model.py.)
+            static_assert(HC_ENC_HANDOFF_MISS && !HC_ENC_HANDOFF_LEVEL, "the run takes the step's hand-off of the byte and the where[] word only");
+            while (t < ns) {
+                uint32_t sv, wh, lv;
+                const uint32_t ja = step(sv, wh, lv);
+                if (ja != kNone) {  // symbol t: not cached, or a level reported: alone
+                    uint32_t sym = lane_read(sv, ja), whw = lane_read(wh, ja);
+                    uint32_t run = min((uint32_t)__builtin_ctz(~(stepmm >> (ja + 1))), (uint32_t)HC_ENC_MISS_RUN_MAX);
+                    for (;;) {
+                        HC_CNT(2);
+                        const uint32_t ent = whw >> 10;
+                        if (ent == 0) {
+                            HC_PROF_BEGIN();
+                            miss_at(sym, whw);
+                            HC_PROF_END(1);
+                        } else {
+                            HC_PROF_BEGIN();
+                            uint32_t pv;
+                            const uint32_t rc = fgk.pc_use(ent, fgk.pc_lane[ent * kRow], pv);
+                            sink.push(rc);
+                            const uint32_t k = fgk.update_fast(pv, [] {});
+                            if (k != 0xFFFFFFFFu) fgk.walk(lane_read(pv, k), pv);
+                            HC_PROF_END(2);
+                        }
+                        ++t;
+                        if (run == 0) break;
+                        --run;
+                        sym = uni(sb[t]);
+                        whw = uni(fgk.T.where[sym]);
+                    }
+                }
+            }
+#else
             // (the path-cache kernel: one regular batch step per pass of this loop)
             while (t < ns) {
                 uint32_t sv, wh, lv;
@@ -1926,6 +2085,7 @@ __global__ __launch_bounds__(64 * HC_WAVES) __attribute__((amdgpu_waves_per_eu(k
                     ++t;
                 }
             }
+#endif
         } else {
             bool small = fgk.nyt >= kSmallNyt;
             while (t < ns) {
