@@ -570,7 +570,10 @@ int hco_fgk_decode_slot(const uint8_t *bits, uint64_t nbits, uint64_t count, uin
                 }
                 s = (uint8_t)((s << 1) | bit_at(bits, pos++));
             }
-            sl_split(t, s);
+            /* huffman.cpp:95-111 splits only for a symbol without a leaf; a stream may name a
+             * known one after the NYT code, whose own leaf is then updated (fg_update's
+             * t->leaf[s] >= 0) */
+            if (t->where[s] == 0) sl_split(t, s);
         } else {
             s = (uint8_t)t->body[x];
         }
