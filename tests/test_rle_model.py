@@ -28,6 +28,7 @@ def test_chunked_rle_equals_serial(oracle_mod):
 import random as _random
 
 import revert_block_model as _rb
+import rle_forge_model as _rf
 
 
 def test_revert_block_model_streams(oracle_mod):
@@ -50,6 +51,86 @@ def test_revert_block_model_random(oracle_mod):
                 want = oracle_mod.undiff(want)
             assert _rb.revert_blocked(sym, diff) == want, (t, diff)
 
+
+
+def _check_tiling(base, gn, gst, gv):
+    """the model's run store (revert_block_model.run_stores) for runs of gn bytes, step gst, first
+    byte gv, each on a canvas of its own: every byte of the run is written exactly once with
+    gv + gst * j mod 256, nothing else is written, and 16-byte stores are aligned"""
+    stride, n = 320, len(gn)
+    k = np.arange(n, dtype=np.int64)
+    go = stride * k + 32 + k % 16  # (stride: a multiple of 16, so base + go takes every residue)
+    out = np.full(stride * n, 0xEE, dtype=np.uint8)
+    hits = np.zeros(stride * n, dtype=np.int64)
+    stores = _rb.run_stores(base, go, gn, gst, gv)
+    for off, data, on in stores:
+        assert data.shape[-1] in (1, 16)
+        if data.shape[-1] == 16:
+            assert not ((base + off[on]) & 15).any()
+    _rb.apply_stores(stores, out, hits=hits)
+    j = np.arange(255, dtype=np.int64)[None, :]
+    inside = j < gn[:, None]
+    idx = (go[:, None] + j)[inside]
+    want = np.full(stride * n, 0xEE, dtype=np.uint8)
+    want[idx] = ((gv[:, None] + gst[:, None] * j) & 255)[inside]
+    want_hits = np.zeros(stride * n, dtype=np.int64)
+    want_hits[idx] = 1
+    bad = np.flatnonzero((hits != want_hits) | (out != want))
+    assert bad.size == 0, (base, [(int(b // stride), int(b % stride)) for b in bad[:8]])
+    return len(stores)
+
+
+def test_run_store_model_tiles_every_run():
+    """every base residue 0..15 x run start residue x length 0..255 x the step set: head bytes,
+    aligned 16-byte units and edge bytes tile the run exactly once, with the carry-less unit
+    arithmetic giving the same bytes as gv + gst * j mod 256"""
+    gn, gst = (a.ravel() for a in np.meshgrid(np.arange(256), np.array(_rf.STEPS), indexing="ij"))
+    gv = (17 * gn + 3 * gst + 5) & 255
+    for base in range(16):
+        steps = _check_tiling(base, gn.astype(np.int64), gst.astype(np.int64), (gv + base).astype(np.int64) & 255)
+        assert steps <= 4 + 8  # <= 15 units at four lanes a step, <= 15 + 15 edge bytes likewise
+
+
+def test_run_store_model_every_step():
+    """all 256 steps (every carry pattern of P, S4 and the 64 * step advance) at a few lengths,
+    every first byte residue mod 4 among them"""
+    gn, gst = (a.ravel() for a in np.meshgrid(np.array([16, 17, 64, 100, 255]), np.arange(256), indexing="ij"))
+    for base in range(16):
+        for first in (0, 0x7F, 0x80, 0xFF, 37 + base):
+            _check_tiling(base, gn.astype(np.int64), gst.astype(np.int64), np.full(gn.size, first, dtype=np.int64))
+
+
+def test_add8_is_a_bytewise_add():
+    rng = np.random.default_rng(8)
+    a, b = (rng.integers(0, 1 << 32, 20000, dtype=np.uint64).astype(np.int64) for _ in range(2))
+    got = _rb.add8(a, b)
+    want = sum((((a >> s) + (b >> s)) & 255) << s for s in (0, 8, 16, 24))
+    assert (got == want).all()
+    assert _rb.add8(0xFF80017F, 0x01808001) == 0x00008180
+
+
+def test_revert_block_model_forged_vectors(oracle_mod):
+    """revert_blocked with the group store equals the oracle on the forged symbol streams
+    (tests/rle_forge_model.py), the output's base residue changing from vector to vector"""
+    for k, (name, sym) in enumerate(_rf.vectors()):
+        want = oracle_mod.unrle(sym)
+        for diff in (False, True):
+            base = (k + 5 * diff) % 16
+            assert _rb.revert_blocked(sym, diff, base) == (oracle_mod.undiff(want) if diff else want), (name, diff)
+
+
+def test_revert_block_model_capacity_path(oracle_mod):
+    """with a capacity inside a run the block goes run by run and byte by byte: the bytes below the
+    capacity are the oracle's"""
+    picks = [v for v in _rf.vectors() if v[0] in ("align/p5-c255-v%d" % _rf.STEPS[(5 * 24 + 23) % 12],
+                                                   "density/r64-k0", "density/all255-k1")]
+    assert len(picks) == 3
+    for name, sym in picks:
+        want = oracle_mod.unrle(sym)
+        for diff in (False, True):
+            w = oracle_mod.undiff(want) if diff else want
+            for cap in (0, 7, len(w) // 2, len(w) - 9, len(w) - 1, len(w)):
+                assert _rb.revert_blocked(sym, diff, 4, cap) == w[:cap], (name, diff, cap)
 
 
 def test_pure_chunk_fast_path(oracle_mod):
