@@ -4,6 +4,7 @@
 // reference) writes for that file alone.
 //
 //   huffman-codec-batch [-c | -d [-r OFFSET:LENGTH]] [-m] [-a [-w WIDTH]] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...
+//   huffman-codec-batch -u OFFSET:PATCHFILE [-u ...] [-o OUTDIR] [-j THREADS] FILE...
 //
 // Compression writes FILE.huf, decompression FILE without its .huf suffix (else FILE.out);
 // with -o into OUTDIR under the same base name. Files are read and written by a pool of
@@ -22,6 +23,14 @@
 // name, through the same call: only the segments that hold the range are uploaded and
 // decoded. Every FILE must then be a container; another one reports "FILE: -r needs a segmented
 // container" and counts as HC_ERR_UNSUPPORTED (65). A range outside a container is HC_ERR_ARG (71).
+//
+// -u OFFSET:PATCHFILE overwrites the raw bytes from OFFSET on with PATCHFILE's bytes in every FILE,
+// each a container, through hc_seg_update: only the segments that the new bytes touch are coded
+// again. It writes FILE.upd (with -o OUTDIR/<base name>.upd) and never touches FILE. Several -u are
+// sorted by offset before the call; patches that overlap, or that reach past a container's raw
+// bytes, are HC_ERR_ARG (71). A FILE that is no container reports "FILE: -u needs a segmented
+// container" (65); a segment that must be decoded and fails reports "FILE: segment K: <message>".
+// -u goes with none of -c, -d, -m, -a, -s, -k and -r.
 #include <unistd.h>
 
 #include <algorithm>
@@ -45,6 +54,7 @@ const char *const kHelp =
     "  huffman-codec-batch [-cm] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch [-cm] -a [-w WIDTH] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch -d [-r OFFSET:LENGTH] [-o OUTDIR] [-j THREADS] FILE... | -h\n"
+    "  huffman-codec-batch -u OFFSET:PATCHFILE [-u ...] [-o OUTDIR] [-j THREADS] FILE...\n"
     "\n"
     "OPTION:\n"
     "  -c/-d  perform compression/decompression\n"
@@ -55,11 +65,13 @@ const char *const kHelp =
     "  -k     with -s: store a CRC-32 of every segment, verified by -d\n"
     "  -r     with -d: write only raw bytes [OFFSET, OFFSET + LENGTH) of every FILE,\n"
     "         each a segmented container\n"
+    "  -u     overwrite the raw bytes from OFFSET on with PATCHFILE's bytes in every FILE,\n"
+    "         each a segmented container; only the segments touched are coded again\n"
     "  -o     output directory (default: next to each input)\n"
     "  -j     file I/O threads (default: 8)\n"
     "  -h     show this help\n"
     "OUTPUT:\n"
-    "  -c: FILE.huf   -d: FILE without .huf (else FILE.out)\n";
+    "  -c: FILE.huf   -d: FILE without .huf (else FILE.out)   -u: FILE.upd\n";
 
 std::string base_name(const std::string &p)
 {
@@ -67,9 +79,10 @@ std::string base_name(const std::string &p)
     return k == std::string::npos ? p : p.substr(k + 1);
 }
 
-std::string out_path(const std::string &in, bool compress, const std::string &dir)
+std::string out_path(const std::string &in, bool compress, bool update, const std::string &dir)
 {
     std::string name = dir.empty() ? in : dir + "/" + base_name(in);
+    if (update) return name + ".upd";
     if (compress) return name + ".huf";
     if (name.size() > 4 && name.compare(name.size() - 4, 4, ".huf") == 0) return name.substr(0, name.size() - 4);
     return name + ".out";
@@ -100,6 +113,22 @@ bool parse_range(const char *arg, uint64_t &offset, uint64_t &length)
     return true;
 }
 
+// "OFFSET:PATCHFILE", the offset decimal and the path not empty
+bool parse_patch(const char *arg, uint64_t &offset, std::string &path)
+{
+    uint64_t v = 0;
+    const char *p = arg;
+    for (; *p >= '0' && *p <= '9'; ++p) {
+        const uint64_t d = (uint64_t)(*p - '0');
+        if (v > (UINT64_MAX - d) / 10) return false;
+        v = v * 10 + d;
+    }
+    if (p == arg || *p != ':' || !p[1]) return false;
+    offset = v;
+    path = p + 1;
+    return true;
+}
+
 template <class F>
 void parallel(size_t n, unsigned threads, F &&f)
 {
@@ -117,12 +146,14 @@ void parallel(size_t n, unsigned threads, F &&f)
 int main(int argc, char *argv[])
 {
     bool compress = true, use_diff = false, use_adapt = false, segmented = false, check = false, ranged = false;
+    bool update = false, coding_option = false;  // -u; any of -c -d -m -a -s -k -r, which -u goes with none of
+    std::vector<std::pair<uint64_t, std::string>> patch_args;  // -u: (offset, patch file)
     uint64_t seg_bytes = 0, r_offset = 0, r_length = 0;
     std::string dir;
     uint64_t width = 512;
     unsigned threads = 8;
     int opt;
-    while ((opt = getopt(argc, argv, ":cdmaw:s:kr:o:j:h")) != -1) {
+    while ((opt = getopt(argc, argv, ":cdmaw:s:kr:u:o:j:h")) != -1) {
         switch (opt) {
         case 'c': compress = true; break;
         case 'd': compress = false; break;
@@ -141,12 +172,29 @@ int main(int argc, char *argv[])
                 return 2;
             }
             break;
+        case 'u': {
+            update = true;
+            uint64_t o = 0;
+            std::string path;
+            if (!parse_patch(optarg, o, path)) {
+                std::cerr << "ERROR: unrecognized option used\n";
+                return 2;
+            }
+            patch_args.emplace_back(o, path);
+            break;
+        }
         case 'o': dir = optarg; break;
         case 'j': threads = (unsigned)std::stoul(optarg); break;
         case 'h': std::cout << kHelp; return 0;
         case ':': std::cerr << "ERROR: missing additional argument\n"; return 1;
         case '?': std::cerr << "ERROR: unrecognized option used\n"; return 2;
         }
+        if (opt == 'c' || opt == 'd' || opt == 'm' || opt == 'a' || opt == 's' || opt == 'k' || opt == 'r')
+            coding_option = true;
+    }
+    if (update && coding_option) {  // a container describes itself: there is nothing to choose
+        std::cerr << "ERROR: unrecognized option used\n";
+        return 2;
     }
     if (check && !(compress && segmented)) {  // a checksum has nowhere to go but a container's index
         std::cerr << "ERROR: unrecognized option used\n";
@@ -178,7 +226,39 @@ int main(int argc, char *argv[])
         in[i].assign(std::istreambuf_iterator<char>(ifs), std::istreambuf_iterator<char>());
     });
 
-    if (compress && segmented) {  // one container per file, all files in one call
+    if (update) {
+        // the patches sorted by offset, their bytes back to back
+        std::stable_sort(patch_args.begin(), patch_args.end(),
+                         [](const auto &a, const auto &b) { return a.first < b.first; });
+        std::vector<hc_seg_patch_t> patches;
+        std::vector<uint8_t> data;
+        for (const auto &pa : patch_args) {
+            std::ifstream ifs(pa.second, std::ios::in | std::ios::binary);
+            if (ifs.fail()) {
+                std::cerr << pa.second << ": ERROR: given input file does not exist\n";
+                return 5;
+            }
+            const std::vector<char> bytes((std::istreambuf_iterator<char>(ifs)), std::istreambuf_iterator<char>());
+            patches.push_back(hc_seg_patch_t{pa.first, bytes.size(), data.size()});
+            data.insert(data.end(), bytes.begin(), bytes.end());
+        }
+        static const uint8_t kSegMagic[8] = {0x48, 0x43, 0x53, 0x45, 0x47, 0x31, 0x00, 0xFF};
+        for (size_t i = 0; i < n; ++i) {
+            if (status[i]) continue;
+            if (in[i].size() < 8 || !std::equal(kSegMagic, kSegMagic + 8, in[i].begin())) {
+                status[i] = -2;  // reported below as HC_ERR_UNSUPPORTED
+                continue;
+            }
+            hc_seg_info_t info;
+            uint64_t cap = 0, len = 0;
+            if (hc_seg_info(in[i].data(), in[i].size(), &info) == HC_OK)
+                cap = hc_seg_update_bound(&info, in[i].size(), patches.data(), (uint32_t)patches.size());
+            out[i].resize(cap ? cap : 1);  // (0: the call refuses the header or the patches, and says which)
+            status[i] = hc_seg_update(in[i].data(), in[i].size(), patches.data(), (uint32_t)patches.size(), data.data(),
+                                      data.size(), out[i].data(), cap, &len, &bad_seg[i]);
+            out[i].resize(status[i] ? 0 : len);
+        }
+    } else if (compress && segmented) {  // one container per file, all files in one call
         const uint32_t fl = (use_diff ? HC_FLAG_DIFF : 0u) | (use_adapt ? HC_FLAG_ADAPT : 0u) |
                             (check ? HC_SEG_CHECK_CRC32 : 0u);
         std::vector<size_t> batch;
@@ -326,9 +406,9 @@ int main(int argc, char *argv[])
             msgs[i] = files[i] + ": ERROR: given input file does not exist\n";
             return;
         }
-        if (status[i] == -1) {
+        if (status[i] == -1 || status[i] == -2) {
+            msgs[i] = files[i] + (status[i] == -1 ? ": -r" : ": -u") + " needs a segmented container\n";
             status[i] = HC_ERR_UNSUPPORTED;
-            msgs[i] = files[i] + ": -r needs a segmented container\n";
             return;
         }
         if (status[i]) {
@@ -336,7 +416,7 @@ int main(int argc, char *argv[])
                       hc_status_message(status[i]);
             return;
         }
-        const std::string op = out_path(files[i], compress, dir);
+        const std::string op = out_path(files[i], compress, update, dir);
         std::ofstream ofs(op, std::ios::out | std::ios::binary);
         if (ofs.fail()) {
             status[i] = 7;  // main.cpp:132-144

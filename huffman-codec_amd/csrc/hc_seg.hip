@@ -22,6 +22,10 @@
 //           for the covered segments only; one that the range covers in part, or any at an offset
 //           that is no multiple of 4, decodes into a slot of the workspace, and a pack launch
 //           (hc_pipe.hip) moves its covered part to its place in out before seg_close
+//   update  a range write (hc_seg_update*): decode the segments that a patch covers in part, lay
+//           the patches over them, code the covered segments, and splice their new streams
+//           and the old container's other bytes into the new container (its own block comment
+//           below has the stages)
 //   items   a call codes one item (an input, or a container and a range of it) or many
 //           (hc_seg_*_batch_dev): the segments of all items lie in one concatenated array, so the
 //           same coder launches serve them all. Each glue stage above is written once, against an
@@ -1022,6 +1026,415 @@ int decode_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, ui
     return decode_launch(item, 1, t, w, in, out, out_len, status, bad_segment, st);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Range write (hc_seg_update*): the container with some raw byte ranges overwritten, without
+// recoding the rest. The host plans the patch list (hc_seg_index.h): the covered segments, in
+// container order, are the entries of one covered array, and those that a patch covers only in part
+// are also the entries of a decoded array. Covered entry c keeps its raw bytes at c full of a
+// staging region (only the container's last segment has another length, and it can only be the
+// last entry, so every entry starts 4-byte aligned) and its new stream in a bound-sized slot.
+//
+//   upatch   the patch records, a chunk per launch as kernel arguments: the pack arrays and the
+//            decoded entries' covered entries
+//   uplan    covered entry c: its segment, its staging range, its slot
+//   uopen    one workgroup: header against the caller's copy, scan of the whole index, the old place
+//            of every covered segment, the decoder's arrays
+//   <decode launch over the decoded entries, into staging; checked containers: their CRC-32>
+//   <pack launch: every patch's bytes over the staging region>
+//   <checked containers: CRC-32 of the covered entries' new raw bytes; encode launch into the slots>
+//   useal    one workgroup: the verdict, and the pieces of the new container: 2 C + 1 of them, old
+//            block j (the old bytes between covered entries j - 1 and j; the first one holds the
+//            header and the index) at 2 j and covered entry j's slot at 2 j + 1, each at the next
+//            multiple of 16 after the one before
+//   usplice  the pieces to their places, 16 bytes per lane; gated by the verdict
+//   uindex   the covered segments' enc_len and crc words over the copied index; gated too
+// ---------------------------------------------------------------------------------------------
+using hc_seg_index::PatchRec;
+using hc_seg_index::UpdPlan;
+constexpr uint32_t kPatchChunk = 48;  // patch records per descriptor launch
+constexpr uint32_t kSpliceChunks = 8;  // 16-byte chunks per lane and tile: a workgroup's tile is 32 KiB
+
+struct UpdWs {
+    PatchRec *recs;
+    uint64_t *pk_src, *pk_len, *pk_dst;                                             // per patch
+    uint64_t *d_cov, *d_in_offs, *d_in_lens, *d_out_offs, *d_out_caps, *d_out_lens;  // per decoded entry
+    int32_t *d_status;
+    uint32_t *d_crc;  // checked containers
+    uint64_t *cov_seg, *old_off, *old_len, *in_offs, *in_lens, *widths, *slot_offs, *slot_caps, *enc_lens;  // per covered entry
+    int32_t *status;
+    uint32_t *crc;  // checked containers
+    uint64_t *pc_src, *pc_dst, *pc_len;  // per piece
+    uint64_t *ctl;  // [0] 1: sealed, the splice may copy; [1] the new length; [2] uopen's verdict
+    uint8_t *stage, *slots;
+    void *awork;
+    uint64_t awork_bytes, total;
+};
+UpdWs carve_upd(void *work, uint64_t P, uint64_t D, uint64_t C, bool check, uint64_t stage_bytes, uint64_t slot_bytes,
+                uint64_t awork_bytes)
+{
+    UpdWs w;
+    uint8_t *p = static_cast<uint8_t *>(work);
+    uint64_t o = 0;
+    auto take = [&](uint64_t bytes) {
+        uint8_t *q = p ? p + o : nullptr;  // null: sizing only
+        o += align16(bytes);
+        return q;
+    };
+    auto take64 = [&](uint64_t n) { return reinterpret_cast<uint64_t *>(take(8 * n)); };
+    w.recs = reinterpret_cast<PatchRec *>(take(sizeof(PatchRec) * P));
+    w.pk_src = take64(P);
+    w.pk_len = take64(P);
+    w.pk_dst = take64(P);
+    w.d_cov = take64(D);
+    w.d_in_offs = take64(D);
+    w.d_in_lens = take64(D);
+    w.d_out_offs = take64(D);
+    w.d_out_caps = take64(D);
+    w.d_out_lens = take64(D);
+    w.d_status = reinterpret_cast<int32_t *>(take(4 * D));
+    w.d_crc = reinterpret_cast<uint32_t *>(take(check ? 4 * D : 0));
+    w.cov_seg = take64(C);
+    w.old_off = take64(C);
+    w.old_len = take64(C);
+    w.in_offs = take64(C);
+    w.in_lens = take64(C);
+    w.widths = take64(C);
+    w.slot_offs = take64(C);
+    w.slot_caps = take64(C);
+    w.enc_lens = take64(C);
+    w.status = reinterpret_cast<int32_t *>(take(4 * C));
+    w.crc = reinterpret_cast<uint32_t *>(take(check ? 4 * C : 0));
+    w.pc_src = take64(2 * C + 1);
+    w.pc_dst = take64(2 * C + 1);
+    w.pc_len = take64(2 * C + 1);
+    w.ctl = take64(4);
+    w.stage = take(stage_bytes);
+    w.slots = take(slot_bytes);
+    w.awork = take(awork_bytes);
+    w.awork_bytes = awork_bytes;
+    w.total = o;
+    return w;
+}
+static_assert(sizeof(PatchRec) == 64, "the work bound of hcodec.h counts this");
+
+// what the stages of a range write share
+struct UpdCall {
+    const uint8_t *in;
+    uint8_t *out;
+    uint64_t in_len, out_cap;
+    uint64_t magic, flags, raw_len, seg_bytes, width, n;  // the header words, the caller's host copy
+    uint64_t full, last, slot_full, cap_full, cap_last;
+    uint64_t P, D, C;
+    uint32_t check;
+    UpdWs w;
+    uint64_t *out_len, *bad_segment;
+    int32_t *status_out;
+};
+
+struct PatchChunk {
+    PatchRec rec[kPatchChunk];
+    PatchRec *recs;
+    uint64_t *pk_src, *pk_len, *pk_dst, *d_cov;
+    uint64_t base;
+    uint32_t count;
+};
+static_assert(sizeof(PatchChunk) <= 3968, "kernel arguments");
+
+__global__ __launch_bounds__(64) void seg_upatch_kernel(PatchChunk c)
+{
+    if (threadIdx.x >= c.count) return;
+    const PatchRec r = c.rec[threadIdx.x];
+    const uint64_t g = c.base + threadIdx.x;
+    c.recs[g] = r;
+    c.pk_src[g] = r.src_off;
+    c.pk_len[g] = r.length;
+    c.pk_dst[g] = r.dst;
+    if (r.dmask & 1) c.d_cov[r.d0] = r.e0;
+    if (r.dmask & 2) c.d_cov[r.d0 + (r.dmask & 1)] = r.e0 + r.cnt - 1;
+}
+
+// covered entry c: its segment (the record that holds it is the last one whose e0 is <= c: a
+// record without new segments shares its e0 with the next one, which the search passes), its
+// staging range and its slot
+__global__ __launch_bounds__(256) void seg_uplan_kernel(UpdCall a)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.C) return;
+    uint64_t lo = 0, hi = a.P;
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (a.w.recs[mid].e0 <= c) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t k = a.w.recs[lo].k0 + (c - a.w.recs[lo].e0);
+    const bool tail = k == a.n - 1;
+    a.w.cov_seg[c] = k;
+    a.w.old_off[c] = 0;
+    a.w.old_len[c] = 0;
+    a.w.in_offs[c] = c * a.full;
+    a.w.in_lens[c] = tail ? a.last : a.full;
+    a.w.widths[c] = a.width;
+    a.w.slot_offs[c] = c * a.slot_full;
+    a.w.slot_caps[c] = tail ? a.cap_last : a.cap_full;
+    a.w.enc_lens[c] = 0;
+    a.w.status[c] = HC_ERR_DEVICE;  // overwritten by the encode launch
+}
+
+// seg_open_kernel's checks and scan for a range write: the old place of every covered segment
+// (found in cov_seg, which ascends, by search), then the decoder's arrays from those. On failure
+// every decoder input is empty: nothing of the container is read. (The encoders still code what
+// the staging region holds, into their slots; the seal's verdict keeps it from out.)
+__global__ __launch_bounds__(kScan) void seg_uopen_kernel(UpdCall a)
+{
+    __shared__ uint64_t part[kScan / 64];
+    __shared__ uint32_t s_err;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) s_err = 0;
+    __syncthreads();
+    bool err = false;
+    const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in);
+    if (tid < 6) {
+        const uint64_t want = tid == 0 ? a.magic : tid == 1 ? a.flags : tid == 2 ? a.raw_len
+                              : tid == 3 ? a.seg_bytes : tid == 4 ? a.width : a.n;
+        if (i64[tid] != want) err = true;
+    }
+    uint64_t carry = align16(index_end(a.n, a.check != 0));
+    for (uint64_t base = 0; base < a.n; base += kScan) {
+        const uint64_t k = base + tid;
+        const bool in = k < a.n;
+        const uint64_t len = in ? i64[6 + k] : 0;
+        const bool big = len > a.in_len;
+        uint64_t total;
+        const uint64_t off = sat_add(carry, block_scan(in && !big ? align16(len) : 0, part, total));
+        if (in) {
+            if (big || off > a.in_len || len > a.in_len - off) err = true;
+            else if (k == a.n - 1 && off + len != a.in_len) err = true;  // truncated, or trailing bytes
+            uint64_t lo = 0, hi = a.C;  // the first entry whose segment is >= k
+            while (lo < hi) {
+                const uint64_t mid = lo + (hi - lo) / 2;
+                if (a.w.cov_seg[mid] < k) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < a.C && a.w.cov_seg[lo] == k) {
+                a.w.old_off[lo] = off;
+                a.w.old_len[lo] = len;
+            }
+        }
+        carry = sat_add(carry, total);
+    }
+    if (err) s_err = 1;
+    __syncthreads();
+    const bool bad = s_err != 0;
+    if (tid == 0) a.w.ctl[2] = bad ? (uint64_t)HC_ERR_SEG_HEADER : 0;
+    for (uint64_t d = tid; d < a.D; d += kScan) {
+        const uint64_t c = a.w.d_cov[d];
+        a.w.d_in_offs[d] = bad ? 0 : a.w.old_off[c];
+        a.w.d_in_lens[d] = bad ? 0 : a.w.old_len[c];
+        a.w.d_out_offs[d] = c * a.full;
+        a.w.d_out_caps[d] = a.w.cov_seg[c] == a.n - 1 ? a.last : a.full;
+        a.w.d_out_lens[d] = 0;
+        a.w.d_status[d] = HC_ERR_DEVICE;  // overwritten by the decode launch
+    }
+}
+
+// The verdict (the lowest failing decoded entry by seg_close_kernel's mapping, then the capacity)
+// and the pieces. Piece p starts at the sum of align16(length) of the pieces before it.
+__global__ __launch_bounds__(kScan) void seg_useal_kernel(UpdCall a)
+{
+    __shared__ uint64_t part[kScan / 64];
+    __shared__ unsigned long long s_bad, s_ebad, s_end;
+    const uint32_t tid = threadIdx.x;
+    const UpdWs &w = a.w;
+    if (tid == 0) {
+        s_bad = kNoSeg;
+        s_ebad = kNoSeg;
+        s_end = 0;
+    }
+    __syncthreads();
+    const int32_t top = (int32_t)w.ctl[2];
+    const uint32_t *want_crc = reinterpret_cast<const uint32_t *>(a.in + 48 + 8 * a.n);
+    if (top == 0) {
+        uint64_t bad = kNoSeg;
+        for (uint64_t d = tid; d < a.D && bad == kNoSeg; d += kScan)
+            if (w.d_status[d] != 0 || w.d_out_lens[d] != w.d_out_caps[d] ||
+                (a.check && w.d_crc[d] != want_crc[w.cov_seg[w.d_cov[d]]]))
+                bad = d;
+        if (bad != kNoSeg) atomicMin(&s_bad, (unsigned long long)bad);
+        bad = kNoSeg;  // (an encoder never fails in a bound-sized slot; if one does, the call must not succeed)
+        for (uint64_t c = tid; c < a.C && bad == kNoSeg; c += kScan)
+            if (w.status[c] != 0) bad = c;
+        if (bad != kNoSeg) atomicMin(&s_ebad, (unsigned long long)bad);
+    }
+    __syncthreads();
+    const uint64_t dbad = s_bad, ebad = s_ebad;
+    int32_t st = top;
+    uint64_t bad_seg = kNoSeg;
+    if (top == 0 && dbad != kNoSeg) {
+        st = w.d_status[dbad];
+        if (st == 0 && w.d_out_lens[dbad] == w.d_out_caps[dbad]) st = HC_ERR_SEG_CHECK;
+        else if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
+        bad_seg = w.cov_seg[w.d_cov[dbad]];
+    } else if (top == 0 && ebad != kNoSeg) {
+        st = w.status[ebad];
+        bad_seg = w.cov_seg[ebad];
+    }
+    if (st != 0) {
+        if (tid == 0) {
+            *a.status_out = st;
+            *a.out_len = 0;
+            if (a.bad_segment) *a.bad_segment = bad_seg;
+            w.ctl[0] = 0;
+            w.ctl[1] = 0;
+        }
+        return;
+    }
+    // the index tiles the old container exactly (uopen), so no sum below can wrap
+    const uint64_t pieces = 2 * a.C + 1;
+    const bool tail_covered = a.C && w.cov_seg[a.C - 1] == a.n - 1;
+    uint64_t carry = 0;
+    for (uint64_t base = 0; base < pieces; base += kScan) {
+        const uint64_t p = base + tid, j = p >> 1;
+        const bool in = p < pieces;
+        uint64_t src = 0, len = 0;
+        if (in && (p & 1)) {
+            src = w.slot_offs[j];
+            len = w.enc_lens[j];
+        } else if (in) {
+            const uint64_t be = j == a.C ? a.in_len : w.old_off[j];
+            src = j == 0 ? 0 : align16(w.old_off[j - 1] + w.old_len[j - 1]);
+            if (src > be) src = be;  // after the container's last segment
+            len = be - src;
+        }
+        uint64_t total;
+        const uint64_t dst = carry + block_scan(in ? align16(len) : 0, part, total);
+        if (in) {
+            w.pc_src[p] = src;
+            w.pc_dst[p] = dst;
+            w.pc_len[p] = len;
+            // the container ends with its last segment's last byte: bytes
+            if (p == (tail_covered ? pieces - 2 : pieces - 1)) s_end = dst + len;
+        }
+        carry += total;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const uint64_t end = s_end;
+    const bool fits = end <= a.out_cap;
+    *a.status_out = fits ? 0 : HC_ERR_CAPACITY;
+    *a.out_len = end;
+    if (a.bad_segment) *a.bad_segment = kNoSeg;
+    w.ctl[0] = fits ? 1 : 0;
+    w.ctl[1] = end;
+}
+
+// The pieces to their places. Output chunk g (16 bytes at 16 g) belongs to the last piece whose
+// start is <= 16 g (a piece without bytes shares its start with the next one). A workgroup takes
+// tiles of 256 x kSpliceChunks chunks, whatever pieces they fall in: two lanes find the pieces of
+// the tile's first and last chunk, and every lane searches between those alone, so a block of
+// hundreds of megabytes is as many workgroups' work as its bytes call for. Sources and
+// destinations are 16-byte aligned. A piece's last chunk, when it is short, goes out byte by byte
+// with its padding zeroed, except at the container's end, where nothing follows the last byte.
+__global__ __launch_bounds__(256) void seg_usplice_kernel(UpdCall a)
+{
+    __shared__ uint64_t s_p[2];
+    const UpdWs &w = a.w;
+    if (w.ctl[0] == 0) return;  // not sealed: nothing is copied
+    const uint64_t end = w.ctl[1], chunks = (end + 15) / 16, pieces = 2 * a.C + 1;
+    constexpr uint64_t kTile = 256ull * kSpliceChunks;
+    auto find = [&](uint64_t x, uint64_t lo, uint64_t hi) {  // pc_dst[lo] <= x; hi: one past the candidates
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (w.pc_dst[mid] <= x) lo = mid;
+            else hi = mid;
+        }
+        return lo;
+    };
+    for (uint64_t g0 = (uint64_t)blockIdx.x * kTile; g0 < chunks; g0 += (uint64_t)gridDim.x * kTile) {
+        const uint64_t g1 = (g0 + kTile < chunks ? g0 + kTile : chunks) - 1;
+        __syncthreads();  // the tile before is done with s_p
+        if (threadIdx.x == 0) s_p[0] = find(16 * g0, 0, pieces);
+        if (threadIdx.x == 64) s_p[1] = find(16 * g1, 0, pieces);
+        __syncthreads();
+        const uint64_t p_lo = s_p[0], p_hi = s_p[1] + 1;
+        const u32x4 *src[kSpliceChunks];
+        uint64_t rest[kSpliceChunks];  // the piece's bytes from this chunk on (0: no chunk)
+        bool last_piece[kSpliceChunks];
+#pragma unroll
+        for (uint32_t i = 0; i < kSpliceChunks; ++i) {
+            const uint64_t g = g0 + (uint64_t)i * 256 + threadIdx.x;
+            rest[i] = 0;
+            src[i] = nullptr;
+            last_piece[i] = false;
+            if (g > g1) continue;
+            const uint64_t p = find(16 * g, p_lo, p_hi), off = 16 * g - w.pc_dst[p], len = w.pc_len[p];
+            if (off >= len) continue;  // (never: a piece's chunks end with its last byte's)
+            rest[i] = len - off;
+            src[i] = reinterpret_cast<const u32x4 *>(((p & 1) ? w.slots : a.in) + w.pc_src[p] + off);
+            last_piece[i] = 16 * g + rest[i] == end;
+        }
+        u32x4 v[kSpliceChunks];
+#pragma unroll
+        for (uint32_t i = 0; i < kSpliceChunks; ++i)
+            if (rest[i] >= 16) v[i] = *src[i];
+#pragma unroll
+        for (uint32_t i = 0; i < kSpliceChunks; ++i) {
+            const uint64_t g = g0 + (uint64_t)i * 256 + threadIdx.x;
+            if (rest[i] >= 16) {
+                reinterpret_cast<u32x4 *>(a.out)[g] = v[i];
+            } else if (rest[i]) {
+                const uint8_t *s8 = reinterpret_cast<const uint8_t *>(src[i]);
+                uint8_t *d8 = a.out + 16 * g;
+                for (uint32_t b = 0; b < (uint32_t)rest[i]; ++b) d8[b] = s8[b];
+                if (!last_piece[i])
+                    for (uint32_t b = (uint32_t)rest[i]; b < 16; ++b) d8[b] = 0;
+            }
+        }
+    }
+}
+
+// the covered segments' index words, from the seal's arrays
+__global__ __launch_bounds__(256) void seg_uindex_kernel(UpdCall a)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.C || a.w.ctl[0] == 0) return;
+    const uint64_t k = a.w.cov_seg[c];
+    reinterpret_cast<uint64_t *>(a.out)[6 + k] = a.w.enc_lens[c];
+    if (a.check) reinterpret_cast<uint32_t *>(a.out)[12 + 2 * a.n + k] = a.w.crc[c];
+}
+
+// the sizes of a range write whose info passed info_ok and whose patches passed patches_ok
+struct UpdSizes {
+    Cuts c;
+    UpdPlan u;
+    uint64_t cap_full, cap_last, slot_full, stage_bytes, slot_bytes, awork_bytes;
+    bool adapt, check;
+};
+UpdSizes upd_sizes(const hc_seg_info_t &info, uint64_t in_len, const hc_seg_patch_t *patches, uint32_t n_patches,
+                   PatchRec *recs)
+{
+    UpdSizes s;
+    (void)info_ok(info, in_len, s.c);
+    s.adapt = (info.flags & HC_FLAG_ADAPT) != 0;
+    s.check = checked(info.flags);
+    s.cap_full = hc_compress_bound(s.c.full, s.adapt);
+    s.cap_last = hc_compress_bound(s.c.last, s.adapt);
+    s.slot_full = align16(s.cap_full);
+    s.u = hc_seg_index::update_plan(s.c, info.raw_len, patches, n_patches, s.slot_full, align16(s.cap_last), recs);
+    s.stage_bytes = align16(s.u.cov_raw);
+    s.slot_bytes = s.u.cov_bound;
+    s.awork_bytes = 0;
+    if (s.adapt && s.u.covered <= kMaxSegs) {
+        const uint64_t e = s.u.covered ? hc::adapt_encode_work_bound(s.u.cov_raw, (uint32_t)s.u.covered) : 0;
+        const uint64_t d = s.u.decoded ? hc::adapt_decode_work_bound(in_len, s.u.dec_raw, (uint32_t)s.u.decoded) : 0;
+        s.awork_bytes = e > d ? e : d;  // the decode launch is over before the encode launch starts
+    }
+    return s;
+}
+UpdWs upd_ws(void *work, const UpdSizes &s, uint32_t n_patches)
+{
+    return carve_upd(work, n_patches, s.u.decoded, s.u.covered, s.check, s.stage_bytes, s.slot_bytes, s.awork_bytes);
+}
+
 // the host batch calls' sub-batch limit, as hc_pipe.hip reads it
 uint64_t pipe_bytes()
 {
@@ -1209,6 +1622,160 @@ int hc_seg_decompress_range(const uint8_t *in, uint64_t in_len, uint64_t offset,
     uint64_t *m = meta.as<uint64_t>();
     const int rc = decode_dev(din.as<uint8_t>(), in_len, &info, offset, length, false, dout.as<uint8_t>(), length, m,
                               reinterpret_cast<int32_t *>(m + 1), m + 2, work.p, wb, st, s0 - idx, span);
+    if (rc) return rc;
+    uint64_t h[4] = {0, 0, 0, 0};
+    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    HC_CK(hipStreamSynchronize(st));
+    const int status = (int32_t)(uint32_t)h[1];
+    *out_len = h[0];
+    if (bad_segment) *bad_segment = h[2];
+    if (status) return status;
+    if (h[0]) HC_CK(hipMemcpy(out, dout.p, h[0], hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_seg_update_segments(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_patch_t *patches,
+                           uint32_t n_patches, uint64_t *n_covered, uint64_t *n_decoded)
+{
+    if (!info || !n_covered || !n_decoded) return HC_ERR_ARG;
+    Cuts c;
+    if (!info_ok(*info, in_len, c) || !hc_seg_index::patches_ok(info->raw_len, patches, n_patches, nullptr))
+        return HC_ERR_ARG;
+    const UpdPlan u = hc_seg_index::update_plan(c, info->raw_len, patches, n_patches, 0, 0, nullptr);
+    *n_covered = u.covered;
+    *n_decoded = u.decoded;
+    return HC_OK;
+}
+
+uint64_t hc_seg_update_bound(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_patch_t *patches,
+                             uint32_t n_patches)
+{
+    if (!info) return 0;
+    Cuts c;
+    if (!info_ok(*info, in_len, c) || !hc_seg_index::patches_ok(info->raw_len, patches, n_patches, nullptr)) return 0;
+    return sat_add(in_len, upd_sizes(*info, in_len, patches, n_patches, nullptr).slot_bytes);
+}
+
+uint64_t hc_seg_update_work_bound(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_patch_t *patches,
+                                  uint32_t n_patches)
+{
+    if (!info) return 0;
+    Cuts c;
+    if (!info_ok(*info, in_len, c)) return 16;  // rejected without a workspace
+    if (!hc_seg_index::patches_ok(info->raw_len, patches, n_patches, nullptr)) return 0;
+    const UpdSizes s = upd_sizes(*info, in_len, patches, n_patches, nullptr);
+    if (s.u.covered > kMaxSegs) return 0;
+    return upd_ws(nullptr, s, n_patches).total;
+}
+
+int hc_seg_update_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, const hc_seg_patch_t *patches,
+                      uint32_t n_patches, const uint8_t *patch_data, uint64_t patch_data_len, uint8_t *out,
+                      uint64_t out_cap, uint64_t *out_len, int32_t *status, uint64_t *bad_segment, void *work,
+                      uint64_t work_bytes, void *stream)
+{
+    if (!in || !info || !out || !out_len || !status || !work) return HC_ERR_ARG;
+    if ((!patches && n_patches) || (!patch_data && patch_data_len)) return HC_ERR_ARG;
+    if (!aligned16(in) || !aligned16(out) || !aligned16(work)) return HC_ERR_ARG;
+    {
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+        if (i0 < o0 ? in_len > o0 - i0 : out_cap > i0 - o0) return HC_ERR_ARG;  // the two buffers overlap
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Cuts c;
+    if (!info_ok(*info, in_len, c)) {
+        seg_reject_kernel<<<1, 1, 0, st>>>(out_len, status, bad_segment);
+        HC_CK(hipGetLastError());
+        return HC_OK;
+    }
+    if (!hc_seg_index::patches_ok(info->raw_len, patches, n_patches, &patch_data_len)) return HC_ERR_ARG;
+    std::vector<PatchRec> recs(n_patches);
+    const UpdSizes s = upd_sizes(*info, in_len, patches, n_patches, recs.data());
+    if (s.u.covered > kMaxSegs) return HC_ERR_ARG;
+    const UpdWs w = upd_ws(work, s, n_patches);
+    if (work_bytes < w.total) return HC_ERR_ARG;
+    const uint64_t P = n_patches, D = s.u.decoded, C = s.u.covered;
+    const UpdCall a{in, out, in_len, out_cap,
+                    get64(kMagic), info->flags & 0xFFFFu, info->raw_len, info->seg_bytes, info->width, c.n,
+                    c.full, c.last, s.slot_full, s.cap_full, s.cap_last,
+                    P, D, C, s.check ? 1u : 0u, w, out_len, bad_segment, status};
+
+    for (uint64_t base = 0; base < P; base += kPatchChunk) {
+        PatchChunk ch;
+        ch.count = (uint32_t)(P - base < kPatchChunk ? P - base : kPatchChunk);
+        memcpy(ch.rec, recs.data() + base, sizeof(PatchRec) * ch.count);
+        ch.recs = w.recs;
+        ch.pk_src = w.pk_src;
+        ch.pk_len = w.pk_len;
+        ch.pk_dst = w.pk_dst;
+        ch.d_cov = w.d_cov;
+        ch.base = base;
+        seg_upatch_kernel<<<1, 64, 0, st>>>(ch);
+    }
+    if (C) seg_uplan_kernel<<<(uint32_t)((C + 255) / 256), 256, 0, st>>>(a);
+    seg_uopen_kernel<<<1, kScan, 0, st>>>(a);
+    HC_CK(hipGetLastError());
+    if (D) {
+        Batch b{in, w.d_in_offs, w.d_in_lens, (uint32_t)D, w.stage, w.d_out_offs, w.d_out_caps, w.d_out_lens, w.d_status, 0};
+        if (s.adapt) HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
+        else HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
+        if (s.check)
+            HC_CK(hc::launch_crc32(w.stage, w.d_out_offs, w.d_out_caps, D, w.d_crc, hc::CrcGate{w.d_status, w.d_out_lens}, st));
+    }
+    if (C) {
+        // every patch's bytes over the staging region, at any byte alignment (an empty patch costs nothing)
+        HC_CK(hc::launch_pack(patch_data, w.pk_src, w.pk_len, n_patches, w.stage, w.pk_dst, st));
+        Batch b{w.stage, w.in_offs, w.in_lens, (uint32_t)C, w.slots, w.slot_offs, w.slot_caps, w.enc_lens, w.status,
+                info->flags & HC_FLAG_DIFF};
+        if (s.check) HC_CK(hc::launch_crc32(w.stage, w.in_offs, w.in_lens, C, w.crc, hc::CrcGate{nullptr, nullptr}, st));
+        if (s.adapt) HC_CK(hc::adapt_encode_batch(b, w.widths, w.awork, w.awork_bytes, st));
+        else HC_CK(hc::launch_encode(b, (info->flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
+    }
+    seg_useal_kernel<<<1, kScan, 0, st>>>(a);
+    // the grid by the longest result there can be: the old container and every slot filled
+    const uint64_t tiles = (in_len + s.slot_bytes) / (4096ull * kSpliceChunks) + 1;
+    seg_usplice_kernel<<<(uint32_t)(tiles < 4096 ? tiles : 4096), 256, 0, st>>>(a);  // (the rest by stride)
+    if (C) seg_uindex_kernel<<<(uint32_t)((C + 255) / 256), 256, 0, st>>>(a);
+    HC_CK(hipGetLastError());
+    return HC_OK;
+}
+
+int hc_seg_update(const uint8_t *in, uint64_t in_len, const hc_seg_patch_t *patches, uint32_t n_patches,
+                  const uint8_t *patch_data, uint64_t patch_data_len, uint8_t *out, uint64_t out_cap, uint64_t *out_len,
+                  uint64_t *bad_segment)
+{
+    if ((!in && in_len) || !out_len || (!out && out_cap)) return HC_ERR_ARG;
+    if ((!patches && n_patches) || (!patch_data && patch_data_len)) return HC_ERR_ARG;
+    auto fail = [&](int rc, uint64_t len) {
+        *out_len = len;
+        if (bad_segment) *bad_segment = kNoSeg;
+        return rc;
+    };
+    hc_seg_info_t info;
+    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0);
+    if (!hc_seg_index::patches_ok(info.raw_len, patches, n_patches, &patch_data_len)) return HC_ERR_ARG;
+    const UpdSizes s = upd_sizes(info, in_len, patches, n_patches, nullptr);
+    if (s.u.covered > kMaxSegs) return HC_ERR_ARG;
+    uint64_t s0 = 0, s1 = 0;
+    if (hc_seg_index::index_scan(in, in_len, s.c.n, s.check, Cover{0, 0}, &s0, &s1) != HC_OK)
+        return fail(HC_ERR_SEG_HEADER, 0);
+    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0);
+    (void)fail(HC_OK, 0);  // (what a HIP error below leaves behind)
+    // the whole container and every patch byte go up, the whole result comes down
+    const uint64_t bound = sat_add(in_len, s.slot_bytes), cap = out_cap < bound ? out_cap : bound;
+    const uint64_t wb = upd_ws(nullptr, s, n_patches).total;
+    hipStream_t st = nullptr;
+    DevBuf din, dpatch, dout, work, meta;
+    HC_CK(din.alloc(in_len + 16));
+    HC_CK(dpatch.alloc(patch_data_len + 16));
+    HC_CK(dout.alloc(cap + 16));
+    HC_CK(work.alloc(wb));
+    HC_CK(meta.alloc(32));
+    HC_CK(hipMemcpyAsync(din.p, in, in_len, hipMemcpyHostToDevice, st));
+    if (patch_data_len) HC_CK(hipMemcpyAsync(dpatch.p, patch_data, patch_data_len, hipMemcpyHostToDevice, st));
+    uint64_t *m = meta.as<uint64_t>();
+    const int rc = hc_seg_update_dev(din.as<uint8_t>(), in_len, &info, patches, n_patches, dpatch.as<uint8_t>(),
+                                     patch_data_len, dout.as<uint8_t>(), cap, m, reinterpret_cast<int32_t *>(m + 1), m + 2,
+                                     work.p, wb, st);
     if (rc) return rc;
     uint64_t h[4] = {0, 0, 0, 0};
     HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));

@@ -141,4 +141,91 @@ inline int index_scan(const uint8_t *in, uint64_t in_len, uint64_t n, bool check
     return HC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Range write (hc_seg_update*): the host's plan of a patch list. The covered segments of a call,
+// in container order, are the entries 0 .. covered - 1 of its covered array; those among them
+// that must be decoded first (every one whose cut does not lie inside ONE patch) are the entries
+// 0 .. decoded - 1 of its decoded array, in the same order. A segment that two patches share
+// belongs to the first of them.
+// ---------------------------------------------------------------------------------------------
+// The patch list's rules: every patch inside raw_len, sorted by offset, none overlapping, and
+// (data_len != nullptr) every source range inside *data_len. n_patches > 0 needs the list.
+inline bool patches_ok(uint64_t raw_len, const hc_seg_patch_t *p, uint32_t n_patches, const uint64_t *data_len)
+{
+    if (n_patches && !p) return false;
+    uint64_t prev_end = 0;
+    for (uint32_t i = 0; i < n_patches; ++i) {
+        if (!range_ok(raw_len, p[i].offset, p[i].length)) return false;
+        if (p[i].offset < prev_end) return false;  // unsorted, or overlapping the one before
+        prev_end = p[i].offset + p[i].length;      // (<= raw_len: no wrap)
+        if (data_len && !range_ok(*data_len, p[i].src_off, p[i].length)) return false;
+    }
+    return true;
+}
+
+// One patch as the device stages read it. Its bytes go to `dst` of the staging region, where
+// covered entry c holds its segment's raw bytes from c full on. It newly covers the segments k0 ..
+// k0 + cnt - 1, the entries e0 .. e0 + cnt - 1; of those, the first (dmask bit 0) and, when cnt > 1,
+// the last (bit 1) are sent to the decoder, as decoded entries d0 and d0 + (dmask & 1).
+struct PatchRec {
+    uint64_t src_off, length, dst;
+    uint64_t k0, cnt, e0;
+    uint64_t d0, dmask;
+};
+struct UpdPlan {
+    uint64_t covered, decoded;
+    uint64_t cov_raw, dec_raw;  // the raw bytes of the covered, of the decoded segments
+    uint64_t cov_bound;         // the sum of align16(bound(cut)) over the covered segments
+};
+// segment k's cut [b, e) (raw: raw_len)
+inline void cut_of(const Cuts &c, uint64_t raw, uint64_t k, uint64_t *b, uint64_t *e)
+{
+    *b = k * c.full;
+    *e = k == c.n - 1 ? raw : *b + c.full;
+}
+// Walks a patch list that passed patches_ok once. recs (or null): n_patches records. bound_full,
+// bound_last: align16(hc_compress_bound) of a full cut and of the last one.
+inline UpdPlan update_plan(const Cuts &c, uint64_t raw, const hc_seg_patch_t *p, uint32_t n_patches, uint64_t bound_full,
+                           uint64_t bound_last, PatchRec *recs)
+{
+    UpdPlan u{0, 0, 0, 0, 0};
+    uint64_t next = 0;  // every segment below this one is placed
+    for (uint32_t i = 0; i < n_patches; ++i) {
+        PatchRec r{p[i].src_off, p[i].length, 0, 0, 0, u.covered, u.decoded, 0};
+        const uint64_t o = p[i].offset, end = o + p[i].length;
+        const Cover cv = range_cover(c, o, p[i].length);
+        if (cv.count) {
+            const uint64_t a = cv.k0, b = cv.k0 + cv.count - 1;
+            // a < next: the patch before ended in segment a, the last entry so far
+            r.dst = (a >= next ? u.covered : u.covered - 1) * c.full + (o - a * c.full);
+            r.k0 = a > next ? a : next;
+            r.cnt = b >= r.k0 ? b - r.k0 + 1 : 0;
+        }
+        if (r.cnt) {
+            const uint64_t kl = r.k0 + r.cnt - 1;
+            uint64_t sb, se;
+            cut_of(c, raw, r.k0, &sb, &se);
+            if (!(o <= sb && end >= se)) {
+                r.dmask |= 1;
+                u.dec_raw += se - sb;
+            }
+            if (r.cnt > 1) {
+                cut_of(c, raw, kl, &sb, &se);
+                if (!(o <= sb && end >= se)) {
+                    r.dmask |= 2;
+                    u.dec_raw += se - sb;
+                }
+            }
+            u.decoded += (r.dmask & 1) + (r.dmask >> 1);
+            u.covered += r.cnt;
+            const bool tail = kl == c.n - 1;
+            u.cov_raw += (r.cnt - 1) * c.full + (tail ? raw - kl * c.full : c.full);
+            u.cov_bound = sat_add(u.cov_bound, sat_add((r.cnt - 1) * bound_full, tail ? bound_last : bound_full));
+            next = kl + 1;
+        }
+        if (recs) recs[i] = r;
+    }
+    return u;
+}
+
 }  // namespace hc_seg_index

@@ -68,6 +68,11 @@ class SegDecItem(ctypes.Structure):
                 ("out_off", ctypes.c_uint64), ("out_cap", ctypes.c_uint64)]
 
 
+class SegPatch(ctypes.Structure):
+    """hc_seg_patch_t: raw bytes [offset, offset + length) become patch_data[src_off .. src_off + length)"""
+    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("src_off", ctypes.c_uint64)]
+
+
 SYNTH = {"noise": 0, "grad": 1, "photo": 2}
 
 _libs = {}           # path -> loaded library
@@ -166,6 +171,16 @@ def _load(path):
     L.hc_seg_decompress_range_work_bound.restype = u64
     L.hc_seg_decompress_range_dev.argtypes = [vp, u64, ctypes.POINTER(SegInfo), u64, u64, vp, u64, vp, vp, vp, vp, u64,
                                               vp]
+    pp = ctypes.POINTER(SegPatch)
+    L.hc_seg_update_segments.argtypes = [ctypes.POINTER(SegInfo), u64, pp, ctypes.c_uint32, ctypes.POINTER(u64),
+                                         ctypes.POINTER(u64)]
+    for f in (L.hc_seg_update_bound, L.hc_seg_update_work_bound):
+        f.argtypes = [ctypes.POINTER(SegInfo), u64, pp, ctypes.c_uint32]
+        f.restype = u64
+    L.hc_seg_update_dev.argtypes = [vp, u64, ctypes.POINTER(SegInfo), pp, ctypes.c_uint32, vp, u64, vp, u64, vp, vp, vp,
+                                    vp, u64, vp]
+    L.hc_seg_update.argtypes = [u8p, u64, pp, ctypes.c_uint32, u8p, u64, u8p, u64, ctypes.POINTER(u64),
+                                ctypes.POINTER(u64)]
     L.hc_seg_compress_batch_work_bound.argtypes = [ctypes.POINTER(SegEncItem), ctypes.c_uint32, ctypes.c_uint32, u64]
     L.hc_seg_compress_batch_work_bound.restype = u64
     L.hc_seg_compress_batch_dev.argtypes = [vp, vp, ctypes.POINTER(SegEncItem), ctypes.c_uint32, ctypes.c_uint32, u64,
@@ -526,6 +541,99 @@ def seg_decompress_range_dev(inp, out, out_len, status, offset, length, bad_segm
                                            _dp(work), work.numel(), _stream_handle(stream))
     if rc:
         raise HCodecError(f"hc_seg_decompress_range_dev failed: {rc}")
+    return work
+
+
+def seg_patches(patches):
+    """a ctypes array of SegPatch from (offset, length, src_off) triples (None when there are none)"""
+    patches = list(patches)
+    if not patches:
+        return None
+    return (SegPatch * len(patches))(*[SegPatch(o, m, s) for o, m, s in patches])
+
+
+def seg_update_segments(info, in_len, patches):
+    """hc_seg_update_segments (host only, no device): (status, covered, decoded) segment counts of
+    a list of (offset, length, src_off) patches"""
+    cov = ctypes.c_uint64(0)
+    dec = ctypes.c_uint64(0)
+    st = lib().hc_seg_update_segments(ctypes.byref(info) if info is not None else None, in_len, seg_patches(patches),
+                                      len(patches), ctypes.byref(cov), ctypes.byref(dec))
+    return st, cov.value, dec.value
+
+
+def seg_update_bound(info, in_len, patches):
+    """hc_seg_update_bound: an output capacity that always suffices (0: the call refuses the arguments)"""
+    return int(lib().hc_seg_update_bound(ctypes.byref(info) if info is not None else None, in_len,
+                                         seg_patches(patches), len(patches)))
+
+
+def seg_update_work_bound(info, in_len, patches):
+    """hc_seg_update_work_bound: the device call's workspace (0: refused; 16: an info that fails)"""
+    return int(lib().hc_seg_update_work_bound(ctypes.byref(info) if info is not None else None, in_len,
+                                              seg_patches(patches), len(patches)))
+
+
+def seg_update(data, patches, full=False, cap=None):
+    """hc_seg_update: (status, the container `data` with the (offset, bytes) patches written into
+    its raw bytes); full: (status, bytes, out_len, bad_segment). cap: the output capacity (default:
+    hc_seg_update_bound). The patches must be sorted by offset and must not overlap."""
+    b, p = _buf(data)
+    tri, blob, at = [], bytearray(), 0
+    for o, pb in patches:
+        tri.append((o, len(pb), at))
+        blob += bytes(pb)
+        at += len(pb)
+    pd, pp = _buf(blob)
+    arr = seg_patches(tri)
+    if cap is None:
+        st, info = seg_info(b)
+        cap = seg_update_bound(info, len(b), tri) if st == 0 else 0
+    out = ctypes.create_string_buffer(max(int(cap), 1))
+    n = ctypes.c_uint64(0)
+    bad = ctypes.c_uint64(NO_SEGMENT)
+    st = lib().hc_seg_update(p, len(b), arr, len(tri), pp, len(pd), ctypes.cast(out, ctypes.c_void_p), cap,
+                             ctypes.byref(n), ctypes.byref(bad))
+    got = out.raw[:n.value] if st == 0 else b""
+    return (st, got, n.value, bad.value) if full else (st, got)
+
+
+def seg_update_dev(inp, patches, patch_data, out, out_len, status, bad_segment=None, info=None, stream=None,
+                   work=None, in_len=None, out_cap=None, patch_data_len=None):
+    """hc_seg_update_dev on CUDA tensors: the container in inp[:in_len] with the (offset, length,
+    src_off) patches, whose bytes lie in the uint8 tensor patch_data (any alignment), into `out`
+    (capacity out_cap, default all of it). info as for seg_decompress_dev. A patch list that fails
+    its rules raises. Returns the workspace."""
+    _check_seg(inp, out, out_len, status, bad_segment)
+    import torch
+    if not isinstance(patch_data, torch.Tensor) or patch_data.dtype != torch.uint8 or not patch_data.is_contiguous() \
+            or patch_data.device != inp.device:
+        raise TypeError("patch_data: expected a contiguous uint8 tensor on the input's device")
+    n = inp.numel() if in_len is None else int(in_len)
+    if n > inp.numel():
+        raise ValueError(f"in_len {n} exceeds the {inp.numel()}-byte input tensor")
+    cap = out.numel() if out_cap is None else int(out_cap)
+    if cap > out.numel():
+        raise ValueError(f"out_cap {cap} exceeds the {out.numel()}-byte output tensor")
+    pdl = patch_data.numel() if patch_data_len is None else int(patch_data_len)
+    if pdl > patch_data.numel():
+        raise ValueError(f"patch_data_len {pdl} exceeds the {patch_data.numel()}-byte tensor")
+    if info is None:
+        head, p = _buf(inp[:min(n, 48)].cpu().numpy().tobytes())
+        info = SegInfo()  # stays all zero when the header does not parse: the call rejects it
+        lib().hc_seg_info(p, n, ctypes.byref(info))
+    patches = list(patches)
+    arr = seg_patches(patches)
+    need = int(lib().hc_seg_update_work_bound(ctypes.byref(info), n, arr, len(patches)))
+    if work is None:
+        work = _work(need, inp.device)
+    _check_work(work, inp.device, need)
+    rc = lib().hc_seg_update_dev(_dp(inp), n, ctypes.byref(info), arr, len(patches),
+                                 _dp(patch_data) if pdl else ctypes.c_void_p(None), pdl, _dp(out), cap, _dp(out_len),
+                                 _dp(status), ctypes.c_void_p(None) if bad_segment is None else _dp(bad_segment),
+                                 _dp(work), work.numel(), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_seg_update_dev failed: {rc}")
     return work
 
 

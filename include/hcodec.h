@@ -368,6 +368,112 @@ int hc_seg_decompress_range_dev(const uint8_t *in, uint64_t in_len, const hc_seg
                                 void *work, uint64_t work_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Range write: the container with some raw byte ranges overwritten, without recoding the rest.
+ * Segment k is the stream hc_compress writes for segment k's bytes alone and the cuts are a
+ * function of the header, so a write that keeps raw_len keeps n, the header and the index size:
+ * only the segments that the new bytes touch are coded again, and every other stream is carried
+ * over byte for byte. raw_len never changes (no append, no truncation).
+ *
+ * Patches. A call takes a list: patch i makes raw bytes [offset, offset + length) of the container
+ * patch_data[src_off .. src_off + length). `patches` is HOST memory, read before the call returns
+ * and never after (the list travels as kernel arguments, in chunks, so a call can be captured in a
+ * graph). Every patch must lie inside raw_len (offset <= raw_len and length <= raw_len - offset);
+ * the patches must be sorted by offset and must not overlap (patches[i+1].offset >=
+ * patches[i].offset + patches[i].length); every [src_off, src_off + length) must lie inside
+ * patch_data_len. Anything else is HC_ERR_ARG, decided on the host. A patch of length 0 is valid
+ * at any offset inside raw_len and touches nothing; n_patches == 0 is valid.
+ *
+ * Covered and decoded segments. A patch of length > 0 covers the segments that a range read of its
+ * bytes covers (the rule above, clamp to n - 1 included); the covered set of a call is the union
+ * over its patches. A covered segment whose whole cut lies inside ONE patch is coded from the patch
+ * alone: its old stream is neither read nor decoded, so overwriting a damaged segment repairs it.
+ * Every other covered segment is decoded whole (and, in a checked container, verified against the
+ * index's CRC-32, as the range decoder does), has the patch bytes laid over it and is coded again.
+ * The rule is per patch: two adjacent patches that together fill a cut still decode it.
+ *
+ * Result. On HC_OK out[0 .. *out_len) is the container with the same 48 header bytes; enc_len[k]
+ * (checked: and crc[k], the CRC-32 of the segment's new raw bytes, before the diff model) replaced
+ * for the covered segments and kept for the others; segment k's stream replaced, for a covered
+ * segment, by the stream hc_compress writes for its cut's new bytes with the container's flags and
+ * width, and copied verbatim for every other one (a damaged uncovered segment is not noticed, as
+ * in a ranged read); every segment at the next multiple of 16 after the one before, with padding 0
+ * after the recoded segments. For a container that this library wrote that is byte for byte what
+ * hc_seg_compress2 gives for the patched raw input with the same flags (check bit included), width
+ * and seg_bytes; with no patch of length > 0 it is the input container.
+ *
+ * Status, in this order (host call):
+ *   1  HC_ERR_ARG         null pointers (device call: in, out or work not 16-byte aligned; [in,
+ *                         in + in_len) and [out, out + out_cap) overlap)    *out_len, *bad_segment not set
+ *   2  HC_ERR_SEG_HEADER  the header fails                                   0, UINT64_MAX
+ *   3  HC_ERR_ARG         the patch list fails its rules (device call: work_bytes below the bound;
+ *                         more than 2^31 - 1 covered segments)              not set
+ *   4  HC_ERR_SEG_HEADER  the index fails: all n entries are scanned and must tile the container
+ *                         exactly, whatever the patches, the empty list included   0, UINT64_MAX
+ *   5  HC_ERR_DEVICE      host call without a device                         0, UINT64_MAX
+ *   6  the status of the lowest failing DECODED segment, by hc_seg_decompress's mapping (the
+ *      coder's own status; another length than the cut: HC_ERR_SEG_SIZE; in a checked container
+ *      the right length with another CRC-32: HC_ERR_SEG_CHECK)               0, its container index
+ *   7  HC_ERR_CAPACITY    the new container is longer than out_cap           the length needed, UINT64_MAX
+ *   8  HC_OK                                                                 the new length, UINT64_MAX
+ * Row 6 comes before row 7, unlike the range decoder: the needed length is known only after the
+ * covered segments are coded, and means nothing when one of them could not be decoded.
+ *
+ * Writes. No byte outside out[0 .. out_cap) is written, whatever the status, and on a non-zero
+ * status no byte of out is written at all.
+ * ------------------------------------------------------------------------------------- */
+typedef struct hc_seg_patch_t {
+    uint64_t offset, length; /* raw bytes [offset, offset + length) of the container ...        */
+    uint64_t src_off;        /* ... become patch_data[src_off .. src_off + length)              */
+} hc_seg_patch_t;
+
+/* Host only, no device. *n_covered, *n_decoded: the segments the call codes again, and those among
+ * them that it decodes first. HC_OK, or HC_ERR_ARG (a null pointer, an info that fails hc_seg_info's
+ * rules for in_len, a patch list that fails the rules above; src_off is not looked at). */
+int hc_seg_update_segments(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_patch_t *patches,
+                           uint32_t n_patches, uint64_t *n_covered, uint64_t *n_decoded);
+/* An out_cap that always suffices: in_len plus the sum over the covered segments of
+ * a16(hc_compress_bound(cut, adaptive)). 0 for arguments that the call refuses. */
+uint64_t hc_seg_update_bound(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_patch_t *patches,
+                             uint32_t n_patches);
+/* The device call's workspace. With P = n_patches, C the covered and D the decoded segments, R and
+ * W their raw bytes, S the sum of a16(hc_compress_bound(cut, adaptive)) over the covered segments
+ * and a16(x) = x rounded up to a multiple of 16:
+ *   a16(64 P) + 3 a16(8 P) + 6 a16(8 D) + a16(4 D) + 9 a16(8 C) + a16(4 C) + 3 a16(8 (2 C + 1)) + 32
+ *   [+ a16(4 D) + a16(4 C) checked] + a16(R) + S
+ *   [+ a16(max(hc_adapt_compress_work_bound(R, C) if C > 0, hc_adapt_decompress_work_bound(in_len,
+ *      W, D) if D > 0)) adaptive]
+ * It grows with the patches and with the segments they cover, never with n. 0 for a null info, a
+ * patch list that fails the rules or more than 2^31 - 1 covered segments; 16 for an info that
+ * fails hc_seg_info's rules (as hc_seg_decompress_work_bound). */
+uint64_t hc_seg_update_work_bound(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_patch_t *patches,
+                                  uint32_t n_patches);
+
+/* Device buffers, asynchronous on `stream`, under the rules of hc_seg_decompress_range_dev: in,
+ * out and work 16-byte aligned; out_len, status and bad_segment (may be NULL) DEVICE pointers; no
+ * device allocation, no host synchronisation, no host read of device memory, every byte of scratch
+ * from `work`. patch_data is a DEVICE pointer of any byte alignment, and so is every src_off. Rows 1
+ * and 3 are the return value; an info that fails hc_seg_info's rules gives HC_ERR_SEG_HEADER as the
+ * device status with return value HC_OK; everything else is the device status.
+ *
+ * Covered segment c (in container order) keeps its raw bytes at c full of a staging region in
+ * `work`: the decoded ones decode straight into it, one pack launch lays every patch's bytes over
+ * it, and one encode launch codes the covered segments into bound-sized slots. The new container
+ * is then spliced from the old one's uncovered runs and the slots, 16 bytes per lane. */
+int hc_seg_update_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info,
+                      const hc_seg_patch_t *patches, uint32_t n_patches,
+                      const uint8_t *patch_data, uint64_t patch_data_len,
+                      uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status,
+                      uint64_t *bad_segment, void *work, uint64_t work_bytes, void *stream);
+
+/* Host buffers, synchronous. The header, the patch list and the index are checked on the host
+ * (rows 2 - 4 need no device); then the container and the patch bytes are uploaded, the device call
+ * runs on the cached scratch of the single calls, and *out_len bytes come back. bad_segment may be
+ * NULL. */
+int hc_seg_update(const uint8_t *in, uint64_t in_len, const hc_seg_patch_t *patches, uint32_t n_patches,
+                  const uint8_t *patch_data, uint64_t patch_data_len,
+                  uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment);
+
+/* ---------------------------------------------------------------------------------------
  * Batches of containers: many inputs, or many (container, range) pairs, in one call whose
  * launches do not grow with the number of items (a directory of mid-sized files; a viewer that
  * fetches many regions of one large image). A launch of the coders takes about as long as its

@@ -27,6 +27,14 @@ on both sides), median of the repeats after warm-up. Prints one JSON line.
                                              at every N, so that a kernel's call count shows whether
                                              its launches grow with N (`rocprofv3 --kernel-trace --stats
                                              --output-format csv`, kernel trace alone, no counters)
+  scripts/seg_bench.py --update              range writes (hc_seg_update, and hc_seg_update_dev under HIP
+                                             events) into the -m container at 64 KiB segments: one 4 KiB
+                                             patch in the middle and a 256 x 256 tile as 256 patches, each
+                                             against what the other calls offer for the job (decode the
+                                             whole, patch, code the whole), with the work bounds of both
+                                             and the rate of the splice (an empty patch list: the whole
+                                             container copied) beside a device copy; --big: the
+                                             16384x16384 photo (4096 segments)
   scripts/seg_bench.py --trace-run           a few segmented calls only, to be run under
                                              `rocprofv3 --kernel-trace --stats -- python ...`
   scripts/seg_bench.py --glue-from STATS.csv adds the glue kernels' share of device time, read
@@ -210,6 +218,136 @@ def range_bench(raw, side, diff, adapt, seg, reps, device):
     return res
 
 
+def update_bench(raw, side, reps, trace=False):
+    """one -m container at 64 KiB segments: the two patch lists through hc_seg_update and
+    hc_seg_update_dev, and through decode + patch + encode of the whole"""
+    import numpy as np
+    import torch
+    L = hc.lib()
+    seg, flags = 65536, hc.HC_FLAG_DIFF
+    st, enc = hc.seg_compress(raw, True, False, side, seg)
+    assert st == 0, st
+    st, info = hc.seg_info(enc)
+    rng = np.random.default_rng(5)
+    mid = (len(raw) // 2) & ~65535
+    y0, x0 = side // 2 + 3, side // 2 + 40
+    lists = {"4KiB": [(mid + 8192, 4096)], "tile256": [((y0 + r) * side + x0, 256) for r in range(256)]}
+    src = ctypes.cast(ctypes.c_char_p(enc), ctypes.c_void_p)
+    cap = 2 * len(enc) + (1 << 20)  # (room for every result here; the bound is about 6x the raw bytes)
+    out = ctypes.create_string_buffer(cap)
+    alt_raw = ctypes.create_string_buffer(len(raw))
+    alt_enc = ctypes.create_string_buffer(cap)
+    k = ctypes.c_uint64(0)
+    whole_work = int(L.hc_seg_decompress_work_bound(ctypes.byref(info), len(enc))) + int(
+        L.hc_seg_compress_work_bound2(len(raw), seg, flags, side))
+    res = {"bytes": len(enc), "segments": info.n_segments, "whole_work_bound": whole_work, "lists": {}}
+
+    host = np.zeros(align16(len(enc)), dtype=np.uint8)
+    host[:len(enc)] = np.frombuffer(enc, dtype=np.uint8)
+    inp = torch.from_numpy(host).cuda()
+    dout = torch.empty(align16(cap), dtype=torch.uint8, device="cuda")
+    draw = torch.empty(len(raw), dtype=torch.uint8, device="cuda")
+    olen = torch.zeros(1, dtype=torch.int64, device="cuda")
+    stt = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+    def events(fn):
+        ts = []
+        for i in range(2 + reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            assert int(stt.item()) == 0
+            if i >= 2:
+                ts.append(e0.elapsed_time(e1))
+        return round(statistics.median(ts), 3), round(min(ts), 3), round(max(ts), 3)
+
+    dec_work = hc.seg_decompress_dev(inp, draw, olen, stt, info=info, in_len=len(enc))
+    enc_work = hc.seg_compress_dev(draw, dout, olen, stt, True, False, side, seg)
+    for name, spans in lists.items():
+        tri, at = [], 0
+        for o, m in spans:
+            tri.append((o, m, at))
+            at += m
+        data = rng.integers(0, 256, at, dtype=np.uint8).tobytes()
+        arr, pd = hc.seg_patches(tri), ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p)
+        st, covered, decoded = hc.seg_update_segments(info, len(enc), tri)
+        assert st == 0
+        if trace:  # the device call alone, for a kernel trace
+            dpd = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+            w = hc.seg_update_dev(inp, tri, dpd, dout, olen, stt, info=info, in_len=len(enc))
+            for _ in range(3):
+                hc.seg_update_dev(inp, tri, dpd, dout, olen, stt, info=info, in_len=len(enc), work=w)
+            torch.cuda.synchronize()
+            continue
+        new_raw = bytearray(raw)
+        for o, m, s in tri:
+            new_raw[o:o + m] = data[s:s + m]
+        new_raw = bytes(new_raw)
+
+        def update():
+            rc = L.hc_seg_update(src, len(enc), arr, len(tri), pd, len(data), ctypes.cast(out, ctypes.c_void_p), cap,
+                                 ctypes.byref(k), None)
+            assert rc == 0, rc
+
+        def alternative():
+            rc = L.hc_seg_decompress(src, len(enc), ctypes.cast(alt_raw, ctypes.c_void_p), len(raw), ctypes.byref(k), None)
+            assert rc == 0, rc
+            for o, m, s in tri:
+                ctypes.memmove(ctypes.addressof(alt_raw) + o, data[s:s + m], m)
+            rc = L.hc_seg_compress2(ctypes.cast(alt_raw, ctypes.c_void_p), len(raw), flags, side, seg,
+                                    ctypes.cast(alt_enc, ctypes.c_void_p), cap, ctypes.byref(k))
+            assert rc == 0, rc
+
+        r = {"patches": len(tri), "covered": covered, "decoded": decoded,
+             "work_bound": hc.seg_update_work_bound(info, len(enc), tri),
+             "update_ms": timed(update, 2, reps)}
+        n_upd = k.value
+        r["decode_patch_encode_ms"] = timed(alternative, 1, reps)
+        assert out.raw[:n_upd] == alt_enc.raw[:k.value]  # the same container, byte for byte
+        st, want = hc.seg_compress(new_raw, True, False, side, seg)
+        assert st == 0 and out.raw[:n_upd] == want
+        r["speedup"] = round(r["decode_patch_encode_ms"][0] / r["update_ms"][0], 2)
+
+        dpd = torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()).cuda()
+        p_src = torch.tensor([s for _, _, s in tri], dtype=torch.int64, device="cuda")
+        p_len = torch.tensor([m for _, m, _ in tri], dtype=torch.int64, device="cuda")
+        p_dst = torch.tensor([o for o, _, _ in tri], dtype=torch.int64, device="cuda")
+        w = hc.seg_update_dev(inp, tri, dpd, dout, olen, stt, info=info, in_len=len(enc))
+        r["device_ms"] = events(lambda: hc.seg_update_dev(inp, tri, dpd, dout, olen, stt, info=info, in_len=len(enc), work=w))
+        assert dout[:n_upd].cpu().numpy().tobytes() == want and int(olen.item()) == n_upd
+
+        def dev_alternative():
+            hc.seg_decompress_dev(inp, draw, olen, stt, info=info, in_len=len(enc), work=dec_work)
+            hc.pack_batch(dpd, p_src, p_len, draw, p_dst)
+            hc.seg_compress_dev(draw, dout, olen, stt, True, False, side, seg, work=enc_work)
+
+        r["device_decode_patch_encode_ms"] = events(dev_alternative)
+        assert dout[:n_upd].cpu().numpy().tobytes() == want
+        r["device_speedup"] = round(r["device_decode_patch_encode_ms"][0] / r["device_ms"][0], 2)
+        # faster by more than the run's own spread: the slowest update under the fastest alternative
+        r["device_faster_beyond_spread"] = r["device_ms"][2] < r["device_decode_patch_encode_ms"][1]
+        r["host_faster_beyond_spread"] = r["update_ms"][2] < r["decode_patch_encode_ms"][1]
+        res["lists"][name] = r
+    # the splice alone: no patch, so the call is the index scan, the seal and one copy of the container
+    empty = torch.empty(16, dtype=torch.uint8, device="cuda")
+    w = hc.seg_update_dev(inp, [], empty, dout, olen, stt, info=info, in_len=len(enc), patch_data_len=0)
+    if trace:
+        for _ in range(3):
+            hc.seg_update_dev(inp, [], empty, dout, olen, stt, info=info, in_len=len(enc), patch_data_len=0, work=w)
+        torch.cuda.synchronize()
+        return None
+    t = events(lambda: hc.seg_update_dev(inp, [], empty, dout, olen, stt, info=info, in_len=len(enc), patch_data_len=0,
+                                         work=w))
+    assert dout[:len(enc)].cpu().numpy().tobytes() == enc
+    c = events(lambda: dout[:len(enc)].copy_(inp[:len(enc)]))
+    res["splice"] = {"identity_ms": t, "bytes_per_s": round(2 * len(enc) / (t[0] * 1e-3)),
+                     "device_copy_ms": c, "device_copy_bytes_per_s": round(2 * len(enc) / (c[0] * 1e-3)),
+                     "note": "bytes read plus bytes written per second; identity_ms also holds the open and seal launches"}
+    return res
+
+
 def _ptrs(bufs):
     return (ctypes.c_void_p * len(bufs))(*[ctypes.cast(b, ctypes.c_void_p) for b in bufs])
 
@@ -352,9 +490,22 @@ def main():
     ap.add_argument("--range", action="store_true")
     ap.add_argument("--big", action="store_true")
     ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--update", action="store_true")
     a = ap.parse_args()
     if not hc.device_ok():
         sys.exit("seg_bench.py needs a gfx950 device: " + hc.device_info())
+    if a.update:
+        side = 4 * SIDE if a.big else SIDE
+        raw = photo(side)
+        res = {"input": f"synthetic photo {side}x{side} ({len(raw)} bytes), -m, 64 KiB segments", "timing":
+               "update_ms, decode_patch_encode_ms: host clock around the synchronous host-buffer calls (copies included); "
+               "device_*: HIP events around the device calls; median [min, max] ms of %d" % a.reps}
+        if a.trace_run:
+            update_bench(raw, side, a.reps, True)
+            return
+        res.update(update_bench(raw, side, a.reps))
+        print(json.dumps(res))
+        return
     if a.batch:
         res = batch_bench(a.reps, a.trace_run)
         if a.trace_run:
