@@ -5,6 +5,7 @@
 //
 //   huffman-codec-batch [-c | -d [-r OFFSET:LENGTH]] [-m] [-a [-w WIDTH]] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...
 //   huffman-codec-batch -u OFFSET:PATCHFILE [-u ...] [-o OUTDIR] [-j THREADS] FILE...
+//   huffman-codec-batch -e TAILFILE [-o OUTDIR] [-j THREADS] FILE...
 //
 // Compression writes FILE.huf, decompression FILE without its .huf suffix (else FILE.out);
 // with -o into OUTDIR under the same base name. Files are read and written by a pool of
@@ -31,6 +32,14 @@
 // bytes, are HC_ERR_ARG (71). A FILE that is no container reports "FILE: -u needs a segmented
 // container" (65); a segment that must be decoded and fails reports "FILE: segment K: <message>".
 // -u goes with none of -c, -d, -m, -a, -s, -k and -r.
+//
+// -e TAILFILE appends TAILFILE's bytes to the raw bytes of every FILE, each a container, through
+// hc_seg_append: only the partly filled last segment and the new ones are coded, and the bytes of
+// every other segment never leave the host. It writes FILE.app (with -o OUTDIR/<base name>.app) and
+// never touches FILE. Exit codes and messages follow -u: a FILE that is no container reports "FILE:
+// -e needs a segmented container" (65); an adaptive container whose width does not divide the tail
+// is HC_ERR_MATRIX_SIZE (6); a last segment that must be decoded and fails reports "FILE: segment K:
+// <message>". -e is given once and goes with none of -c, -d, -m, -a, -s, -k, -r and -u.
 #include <unistd.h>
 
 #include <algorithm>
@@ -55,6 +64,7 @@ const char *const kHelp =
     "  huffman-codec-batch [-cm] -a [-w WIDTH] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch -d [-r OFFSET:LENGTH] [-o OUTDIR] [-j THREADS] FILE... | -h\n"
     "  huffman-codec-batch -u OFFSET:PATCHFILE [-u ...] [-o OUTDIR] [-j THREADS] FILE...\n"
+    "  huffman-codec-batch -e TAILFILE [-o OUTDIR] [-j THREADS] FILE...\n"
     "\n"
     "OPTION:\n"
     "  -c/-d  perform compression/decompression\n"
@@ -67,11 +77,13 @@ const char *const kHelp =
     "         each a segmented container\n"
     "  -u     overwrite the raw bytes from OFFSET on with PATCHFILE's bytes in every FILE,\n"
     "         each a segmented container; only the segments touched are coded again\n"
+    "  -e     append TAILFILE's bytes to the raw bytes of every FILE, each a segmented\n"
+    "         container; only the open last segment and the new ones are coded\n"
     "  -o     output directory (default: next to each input)\n"
     "  -j     file I/O threads (default: 8)\n"
     "  -h     show this help\n"
     "OUTPUT:\n"
-    "  -c: FILE.huf   -d: FILE without .huf (else FILE.out)   -u: FILE.upd\n";
+    "  -c: FILE.huf   -d: FILE without .huf (else FILE.out)   -u: FILE.upd   -e: FILE.app\n";
 
 std::string base_name(const std::string &p)
 {
@@ -79,10 +91,11 @@ std::string base_name(const std::string &p)
     return k == std::string::npos ? p : p.substr(k + 1);
 }
 
-std::string out_path(const std::string &in, bool compress, bool update, const std::string &dir)
+std::string out_path(const std::string &in, bool compress, bool update, bool append, const std::string &dir)
 {
     std::string name = dir.empty() ? in : dir + "/" + base_name(in);
     if (update) return name + ".upd";
+    if (append) return name + ".app";
     if (compress) return name + ".huf";
     if (name.size() > 4 && name.compare(name.size() - 4, 4, ".huf") == 0) return name.substr(0, name.size() - 4);
     return name + ".out";
@@ -148,12 +161,14 @@ int main(int argc, char *argv[])
     bool compress = true, use_diff = false, use_adapt = false, segmented = false, check = false, ranged = false;
     bool update = false, coding_option = false;  // -u; any of -c -d -m -a -s -k -r, which -u goes with none of
     std::vector<std::pair<uint64_t, std::string>> patch_args;  // -u: (offset, patch file)
+    bool append = false;    // -e
+    std::string tail_path;  // -e: the file whose bytes are appended
     uint64_t seg_bytes = 0, r_offset = 0, r_length = 0;
     std::string dir;
     uint64_t width = 512;
     unsigned threads = 8;
     int opt;
-    while ((opt = getopt(argc, argv, ":cdmaw:s:kr:u:o:j:h")) != -1) {
+    while ((opt = getopt(argc, argv, ":cdmaw:s:kr:u:e:o:j:h")) != -1) {
         switch (opt) {
         case 'c': compress = true; break;
         case 'd': compress = false; break;
@@ -183,6 +198,14 @@ int main(int argc, char *argv[])
             patch_args.emplace_back(o, path);
             break;
         }
+        case 'e':
+            if (append || !*optarg) {  // one tail, and a path
+                std::cerr << "ERROR: unrecognized option used\n";
+                return 2;
+            }
+            append = true;
+            tail_path = optarg;
+            break;
         case 'o': dir = optarg; break;
         case 'j': threads = (unsigned)std::stoul(optarg); break;
         case 'h': std::cout << kHelp; return 0;
@@ -192,7 +215,7 @@ int main(int argc, char *argv[])
         if (opt == 'c' || opt == 'd' || opt == 'm' || opt == 'a' || opt == 's' || opt == 'k' || opt == 'r')
             coding_option = true;
     }
-    if (update && coding_option) {  // a container describes itself: there is nothing to choose
+    if ((update || append) && (coding_option || (update && append))) {  // a container describes itself: there is nothing to choose
         std::cerr << "ERROR: unrecognized option used\n";
         return 2;
     }
@@ -256,6 +279,28 @@ int main(int argc, char *argv[])
             out[i].resize(cap ? cap : 1);  // (0: the call refuses the header or the patches, and says which)
             status[i] = hc_seg_update(in[i].data(), in[i].size(), patches.data(), (uint32_t)patches.size(), data.data(),
                                       data.size(), out[i].data(), cap, &len, &bad_seg[i]);
+            out[i].resize(status[i] ? 0 : len);
+        }
+    } else if (append) {
+        std::ifstream tfs(tail_path, std::ios::in | std::ios::binary);
+        if (tfs.fail()) {
+            std::cerr << tail_path << ": ERROR: given input file does not exist\n";
+            return 5;
+        }
+        const std::vector<uint8_t> tail((std::istreambuf_iterator<char>(tfs)), std::istreambuf_iterator<char>());
+        static const uint8_t kSegMagic[8] = {0x48, 0x43, 0x53, 0x45, 0x47, 0x31, 0x00, 0xFF};
+        for (size_t i = 0; i < n; ++i) {
+            if (status[i]) continue;
+            if (in[i].size() < 8 || !std::equal(kSegMagic, kSegMagic + 8, in[i].begin())) {
+                status[i] = -3;  // reported below as HC_ERR_UNSUPPORTED
+                continue;
+            }
+            hc_seg_info_t info;
+            uint64_t cap = 0, len = 0;
+            if (hc_seg_info(in[i].data(), in[i].size(), &info) == HC_OK) cap = hc_seg_append_bound(&info, in[i].size(), tail.size());
+            out[i].resize(cap ? cap : 1);  // (0: the call refuses the header or the tail's length, and says which)
+            status[i] = hc_seg_append(in[i].data(), in[i].size(), tail.data(), tail.size(), out[i].data(), cap, &len,
+                                      &bad_seg[i]);
             out[i].resize(status[i] ? 0 : len);
         }
     } else if (compress && segmented) {  // one container per file, all files in one call
@@ -406,8 +451,8 @@ int main(int argc, char *argv[])
             msgs[i] = files[i] + ": ERROR: given input file does not exist\n";
             return;
         }
-        if (status[i] == -1 || status[i] == -2) {
-            msgs[i] = files[i] + (status[i] == -1 ? ": -r" : ": -u") + " needs a segmented container\n";
+        if (status[i] == -1 || status[i] == -2 || status[i] == -3) {
+            msgs[i] = files[i] + (status[i] == -1 ? ": -r" : status[i] == -2 ? ": -u" : ": -e") + " needs a segmented container\n";
             status[i] = HC_ERR_UNSUPPORTED;
             return;
         }
@@ -416,7 +461,7 @@ int main(int argc, char *argv[])
                       hc_status_message(status[i]);
             return;
         }
-        const std::string op = out_path(files[i], compress, update, dir);
+        const std::string op = out_path(files[i], compress, update, append, dir);
         std::ofstream ofs(op, std::ios::out | std::ios::binary);
         if (ofs.fail()) {
             status[i] = 7;  // main.cpp:132-144

@@ -26,6 +26,9 @@
 //           the patches over them, code the covered segments, and splice their new streams
 //           and the old container's other bytes into the new container (its own block comment
 //           below has the stages)
+//   append  raw bytes added behind a container (hc_seg_append*): decode the partly filled last segment,
+//           lay the new bytes behind it, code that segment and the new ones, and splice them behind
+//           the kept segments under a new index (its own block comment below has the stages)
 //   items   a call codes one item (an input, or a container and a range of it) or many
 //           (hc_seg_*_batch_dev): the segments of all items lie in one concatenated array, so the
 //           same coder launches serve them all. Each glue stage above is written once, against an
@@ -1435,6 +1438,411 @@ UpdWs upd_ws(void *work, const UpdSizes &s, uint32_t n_patches)
     return carve_upd(work, n_patches, s.u.decoded, s.u.covered, s.check, s.stage_bytes, s.slot_bytes, s.awork_bytes);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Append (hc_seg_append*): the container of raw followed by add from the container of raw, without recoding
+// the rest. The host plans the cuts (hc_seg_index.h): segments 0 .. K - 1 are kept, and the coded
+// segments K .. n' - 1 hold the open tail (old segment n - 1 when it is not yet a complete cut; the
+// only segment that is ever decoded) and the added bytes. Coded entry c keeps its raw bytes at
+// c full of a staging region and its new stream in a bound-sized slot, as in the range write.
+//
+//   aopen    one workgroup: header against the caller's copy, scan of the whole index, the kept
+//            block (segment 0's first byte to segment K - 1's last), the decoder's one entry
+//   <decode launch of old segment n - 1 to staging offset 0; checked containers: its CRC-32>
+//   aplan    coded entry c: its staging range, its slot, its own part of the added bytes as one
+//            pack range (so a large append packs on as many workgroups as it codes segments)
+//   <pack launch: the added bytes behind the open tail, at any byte alignment>
+//   <checked containers: CRC-32 of the coded cuts; encode launch into the slots>
+//   aseal    one workgroup: the verdict, the new segments' places, and the copy pieces in
+//            seg_usplice_kernel's layout (2 C + 1 of them: the kept block at 0, coded entry c's
+//            slot at 2 c + 1, nothing at the other even places)
+//   usplice  the range write's splice kernel moves the pieces, 16 bytes per lane; gated
+//   aindex   the new header words, enc_len[0 .. n'), crc[0 .. n') (kept entries from the old index
+//            at its old place), the zero padding up to the first segment; gated
+//
+// The host call runs the same stages on a compact upload (header, index, old segment n - 1's
+// stream: `skip` is what that stream's offset loses) and in gather mode: the kept block stays on
+// the host, the pieces are the slots alone, packed from byte 0 of a device buffer, and aindex is
+// not run (the host writes the index from the coded entries' words).
+// ---------------------------------------------------------------------------------------------
+using hc_seg_index::AppPlan;
+
+struct AppWs {
+    uint64_t *in_offs, *in_lens, *widths, *slot_offs, *slot_caps, *enc_lens, *pk_src, *pk_len, *pk_dst;  // per coded entry
+    int32_t *status;
+    uint32_t *crc;  // checked containers
+    uint64_t *pc_src, *pc_dst, *pc_len;  // per piece
+    uint64_t *d_in_off, *d_in_len, *d_out_off, *d_out_cap, *d_out_len;  // the decoder's one entry
+    int32_t *d_status;
+    uint32_t *d_crc;  // checked containers
+    // [0] 1: sealed, the splice may copy; [1] the spliced bytes' end; [2] aopen's verdict; [3], [4] the
+    // kept block's first byte in `in` and its length
+    uint64_t *ctl;
+    uint8_t *stage, *slots;
+    void *awork;
+    uint64_t awork_bytes, total;
+};
+AppWs carve_app(void *work, uint64_t C, bool check, uint64_t stage_bytes, uint64_t slot_bytes, uint64_t awork_bytes)
+{
+    AppWs w;
+    uint8_t *p = static_cast<uint8_t *>(work);
+    uint64_t o = 0;
+    auto take = [&](uint64_t bytes) {
+        uint8_t *q = p ? p + o : nullptr;  // null: sizing only
+        o += align16(bytes);
+        return q;
+    };
+    auto take64 = [&](uint64_t n) { return reinterpret_cast<uint64_t *>(take(8 * n)); };
+    w.in_offs = take64(C);
+    w.in_lens = take64(C);
+    w.widths = take64(C);
+    w.slot_offs = take64(C);
+    w.slot_caps = take64(C);
+    w.enc_lens = take64(C);
+    w.pk_src = take64(C);
+    w.pk_len = take64(C);
+    w.pk_dst = take64(C);
+    w.status = reinterpret_cast<int32_t *>(take(4 * C));
+    w.crc = reinterpret_cast<uint32_t *>(take(check ? 4 * C : 0));
+    w.pc_src = take64(2 * C + 1);
+    w.pc_dst = take64(2 * C + 1);
+    w.pc_len = take64(2 * C + 1);
+    w.d_in_off = take64(1);
+    w.d_in_len = take64(1);
+    w.d_out_off = take64(1);
+    w.d_out_cap = take64(1);
+    w.d_out_len = take64(1);
+    w.d_status = reinterpret_cast<int32_t *>(take(4));
+    w.d_crc = reinterpret_cast<uint32_t *>(take(check ? 4 : 0));
+    w.ctl = take64(8);
+    w.stage = take(stage_bytes);
+    w.slots = take(slot_bytes);
+    w.awork = take(awork_bytes);
+    w.awork_bytes = awork_bytes;
+    w.total = o;
+    return w;
+}
+
+// what the stages of an append share
+struct AppCall {
+    const uint8_t *in;
+    uint8_t *out;
+    uint64_t in_len, out_cap, skip;
+    uint64_t magic, flags, raw_len, seg_bytes, width, n;  // the old header words, the caller's host copy
+    uint64_t full, last;                                  // the old cuts
+    uint64_t new_raw, new_n, new_last;                    // the new header words and the new last cut
+    uint64_t K, C, D, tail, add_len;
+    uint64_t slot_full, cap_full, cap_last;
+    uint32_t check, gather;
+    AppWs w;
+    uint64_t *out_len, *bad_segment;
+    int32_t *status_out;
+};
+
+// seg_uopen_kernel's checks and scan for an append: where the kept block ends and where old segment
+// n - 1 lies. On failure the decoder's input is empty: nothing of the container is read.
+__global__ __launch_bounds__(kScan) void seg_aopen_kernel(AppCall a)
+{
+    __shared__ uint64_t part[kScan / 64];
+    __shared__ uint32_t s_err;
+    __shared__ uint64_t s_kept_end, s_last_off, s_last_len;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t first = align16(index_end(a.n, a.check != 0));
+    if (tid == 0) {
+        s_err = 0;
+        s_kept_end = first;
+        s_last_off = s_last_len = 0;
+    }
+    __syncthreads();
+    bool err = false;
+    const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in);
+    if (tid < 6) {
+        const uint64_t want = tid == 0 ? a.magic : tid == 1 ? a.flags : tid == 2 ? a.raw_len
+                              : tid == 3 ? a.seg_bytes : tid == 4 ? a.width : a.n;
+        if (i64[tid] != want) err = true;
+    }
+    uint64_t carry = first;
+    for (uint64_t base = 0; base < a.n; base += kScan) {
+        const uint64_t k = base + tid;
+        const bool in = k < a.n;
+        const uint64_t len = in ? i64[6 + k] : 0;
+        const bool big = len > a.in_len;
+        uint64_t total;
+        const uint64_t off = sat_add(carry, block_scan(in && !big ? align16(len) : 0, part, total));
+        if (in) {
+            if (big || off > a.in_len || len > a.in_len - off) {
+                err = true;
+            } else if (k == a.n - 1 && off + len != a.in_len) {
+                err = true;  // truncated, or trailing bytes
+            } else {
+                if (k + 1 == a.K) s_kept_end = off + len;
+                if (k == a.n - 1) {
+                    s_last_off = off;
+                    s_last_len = len;
+                }
+            }
+        }
+        carry = sat_add(carry, total);
+    }
+    if (err) s_err = 1;
+    __syncthreads();
+    if (tid != 0) return;
+    const bool bad = s_err != 0;
+    const AppWs &w = a.w;
+    w.ctl[2] = bad ? (uint64_t)HC_ERR_SEG_HEADER : 0;
+    w.ctl[3] = first;
+    w.ctl[4] = bad ? 0 : s_kept_end - first;  // (K == 0: nothing is kept)
+    if (a.D) {
+        w.d_in_off[0] = bad ? 0 : s_last_off - a.skip;
+        w.d_in_len[0] = bad ? 0 : s_last_len;
+        w.d_out_off[0] = 0;
+        w.d_out_cap[0] = a.last;
+        w.d_out_len[0] = 0;
+        w.d_status[0] = HC_ERR_DEVICE;  // overwritten by the decode launch
+    }
+}
+
+// coded entry c: its staging range, its slot, and the added bytes that fall into its cut: the
+// staging region holds the open tail in [0, tail) and the added bytes in [tail, tail + add_len)
+__global__ __launch_bounds__(256) void seg_aplan_kernel(AppCall a)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.C) return;
+    const AppWs &w = a.w;
+    const bool tail = c == a.C - 1;
+    const uint64_t b = c * a.full, e = b + (tail ? a.new_last : a.full);
+    w.in_offs[c] = b;
+    w.in_lens[c] = e - b;
+    w.widths[c] = a.width;
+    w.slot_offs[c] = c * a.slot_full;
+    w.slot_caps[c] = tail ? a.cap_last : a.cap_full;
+    w.enc_lens[c] = 0;
+    w.status[c] = HC_ERR_DEVICE;  // overwritten by the encode launch
+    const uint64_t lo = b > a.tail ? b : a.tail;  // (e <= tail + add_len: the cuts end with the added bytes)
+    w.pk_src[c] = lo < e ? lo - a.tail : 0;
+    w.pk_len[c] = lo < e ? e - lo : 0;
+    w.pk_dst[c] = lo < e ? lo : 0;
+}
+
+// The verdict (the decoded segment by seg_close_kernel's mapping, then the capacity), the new
+// segments' places and the pieces. The kept block goes to align16 of the new index end, the coded
+// entries follow it, each at the next multiple of 16. In gather mode the kept block is no piece and
+// the places count from the first coded segment's.
+__global__ __launch_bounds__(kScan) void seg_aseal_kernel(AppCall a)
+{
+    __shared__ uint64_t part[kScan / 64];
+    __shared__ unsigned long long s_ebad, s_end;
+    const uint32_t tid = threadIdx.x;
+    const AppWs &w = a.w;
+    const int32_t top = (int32_t)w.ctl[2];
+    const uint64_t kept_len = w.ctl[4];
+    const uint64_t first = align16(index_end(a.new_n, a.check != 0)), base0 = first + align16(kept_len);
+    if (tid == 0) {
+        s_ebad = kNoSeg;
+        s_end = first + kept_len;  // no coded entry: nothing is added, the kept block is the old container's rest
+    }
+    __syncthreads();
+    if (top == 0) {  // (an encoder never fails in a bound-sized slot; if one does, the call must not succeed)
+        uint64_t bad = kNoSeg;
+        for (uint64_t c = tid; c < a.C && bad == kNoSeg; c += kScan)
+            if (w.status[c] != 0) bad = c;
+        if (bad != kNoSeg) atomicMin(&s_ebad, (unsigned long long)bad);
+    }
+    __syncthreads();
+    const uint64_t ebad = s_ebad;
+    int32_t st = top;
+    uint64_t bad_seg = kNoSeg;
+    const uint32_t *want_crc = reinterpret_cast<const uint32_t *>(a.in + 48 + 8 * a.n);
+    if (top == 0 && a.D &&
+        (w.d_status[0] != 0 || w.d_out_len[0] != w.d_out_cap[0] || (a.check && w.d_crc[0] != want_crc[a.n - 1]))) {
+        st = w.d_status[0];
+        if (st == 0 && w.d_out_len[0] == w.d_out_cap[0]) st = HC_ERR_SEG_CHECK;
+        else if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
+        bad_seg = a.n - 1;
+    } else if (top == 0 && ebad != kNoSeg) {
+        st = w.status[ebad];
+        bad_seg = a.K + ebad;
+    }
+    if (st != 0) {
+        if (tid == 0) {
+            *a.status_out = st;
+            *a.out_len = 0;
+            if (a.bad_segment) *a.bad_segment = bad_seg;
+            w.ctl[0] = 0;
+            w.ctl[1] = 0;
+        }
+        return;
+    }
+    // the index tiles the old container exactly (aopen) and every enc_len fits its slot, so no sum below can wrap
+    const uint64_t shift = a.gather ? base0 : 0;
+    if (tid == 0) {
+        w.pc_src[0] = w.ctl[3];
+        w.pc_dst[0] = a.gather ? 0 : first;
+        w.pc_len[0] = a.gather ? 0 : kept_len;
+    }
+    uint64_t carry = base0;
+    for (uint64_t base = 0; base < a.C; base += kScan) {
+        const uint64_t c = base + tid;
+        const bool in = c < a.C;
+        const uint64_t len = in ? w.enc_lens[c] : 0;
+        uint64_t total;
+        const uint64_t dst = carry + block_scan(in ? align16(len) : 0, part, total);
+        if (in) {
+            w.pc_src[2 * c + 1] = w.slot_offs[c];
+            w.pc_dst[2 * c + 1] = dst - shift;
+            w.pc_len[2 * c + 1] = len;
+            w.pc_src[2 * c + 2] = 0;  // (the range write's old block between two covered entries: none here)
+            w.pc_dst[2 * c + 2] = dst + align16(len) - shift;
+            w.pc_len[2 * c + 2] = 0;
+            if (c == a.C - 1) s_end = dst + len;  // the container ends with its last segment's last byte
+        }
+        carry += total;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const uint64_t end = s_end;
+    const bool fits = end <= a.out_cap;
+    *a.status_out = fits ? 0 : HC_ERR_CAPACITY;
+    *a.out_len = end;
+    if (a.bad_segment) *a.bad_segment = kNoSeg;
+    w.ctl[0] = fits ? 1 : 0;
+    w.ctl[1] = end - shift;
+}
+
+// The new header and index in front of the spliced bytes: header words 0 .. 5 (raw_len and
+// n_segments new), enc_len[0 .. n') and, in a checked container, crc[0 .. n'): the kept entries from
+// the old index, whose crc words lie at their old place behind 8 n bytes of lengths, the coded
+// entries from the seal's arrays; then the zero padding up to the first segment.
+__global__ __launch_bounds__(256) void seg_aindex_kernel(AppCall a)
+{
+    const AppWs &w = a.w;
+    if (w.ctl[0] == 0) return;  // not sealed: nothing is written
+    const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in);
+    const uint32_t *i32 = reinterpret_cast<const uint32_t *>(a.in);
+    uint64_t *o64 = reinterpret_cast<uint64_t *>(a.out);
+    uint32_t *o32 = reinterpret_cast<uint32_t *>(a.out);
+    const uint64_t idx_end = index_end(a.new_n, a.check != 0);
+    if (blockIdx.x == 0 && threadIdx.x >= 8 && threadIdx.x < 14) {
+        const uint32_t t = threadIdx.x - 8;
+        o64[t] = t == 0 ? a.magic : t == 1 ? a.flags : t == 2 ? a.new_raw : t == 3 ? a.seg_bytes : t == 4 ? a.width : a.new_n;
+    }
+    for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < a.new_n; k += (uint64_t)gridDim.x * 256) {
+        o64[6 + k] = k < a.K ? i64[6 + k] : w.enc_lens[k - a.K];
+        if (a.check) o32[12 + 2 * a.new_n + k] = k < a.K ? i32[12 + 2 * a.n + k] : w.crc[k - a.K];
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (align16(idx_end) - idx_end) / 4) o32[idx_end / 4 + threadIdx.x] = 0;
+}
+
+// the sizes of an append whose info passed info_ok
+struct AppSizes {
+    Cuts c;
+    AppPlan p;
+    uint64_t cap_full, cap_last, slot_full, slot_bytes, awork_bytes;
+    bool adapt, check;
+};
+// HC_OK, or the status that the host decides (HC_ERR_ARG, HC_ERR_MATRIX_SIZE). dec_in: the decoded
+// segment's stream length when the host knows it (the host call); null: the longest stream this
+// library writes for that cut, or in_len when that is less.
+int app_sizes(const hc_seg_info_t &info, uint64_t in_len, uint64_t add_len, const uint64_t *dec_in, AppSizes &s)
+{
+    (void)info_ok(info, in_len, s.c);
+    s.adapt = (info.flags & HC_FLAG_ADAPT) != 0;
+    s.check = checked(info.flags);
+    const int rc = hc_seg_index::append_plan(s.c, info.raw_len, add_len, info.seg_bytes, s.adapt, info.width, &s.p);
+    if (rc) return rc;
+    if (s.p.coded > kMaxSegs) return HC_ERR_ARG;
+    s.cap_full = hc_compress_bound(s.c.full, s.adapt);
+    s.cap_last = hc_compress_bound(s.p.nc.last, s.adapt);
+    s.slot_full = align16(s.cap_full);
+    s.slot_bytes = hc_seg_index::append_slots(s.p, s.slot_full, align16(s.cap_last));
+    s.awork_bytes = 0;
+    if (s.adapt) {
+        const uint64_t old_bound = hc_compress_bound(s.c.last, 1);
+        const uint64_t din = dec_in ? *dec_in : (in_len < old_bound ? in_len : old_bound);
+        const uint64_t e = s.p.coded ? hc::adapt_encode_work_bound(s.p.stage, (uint32_t)s.p.coded) : 0;
+        const uint64_t d = s.p.decoded ? hc::adapt_decode_work_bound(din, s.c.last, 1) : 0;
+        s.awork_bytes = e > d ? e : d;  // the decode launch is over before the encode launch starts
+    }
+    return HC_OK;
+}
+AppWs app_ws(void *work, const AppSizes &s)
+{
+    return carve_app(work, s.p.coded, s.check, s.p.stage, s.slot_bytes, s.awork_bytes);
+}
+
+// hc_seg_append_dev, and the host call's device part (gather; `in` is then its compact upload and
+// `out` its buffer for the coded streams, while in_len and out_cap stay the caller's)
+int append_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, const uint8_t *add, uint64_t add_len,
+               uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status, uint64_t *bad_segment, void *work,
+               uint64_t work_bytes, void *stream, bool gather, uint64_t skip, const uint64_t *dec_in)
+{
+    if (!in || !info || !out || !out_len || !status || !work || (!add && add_len)) return HC_ERR_ARG;
+    if (!aligned16(in) || !aligned16(out) || !aligned16(work)) return HC_ERR_ARG;
+    if (!gather) {
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+        if (i0 < o0 ? in_len > o0 - i0 : out_cap > i0 - o0) return HC_ERR_ARG;  // the two buffers overlap
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Cuts c;
+    if (!info_ok(*info, in_len, c)) {
+        seg_reject_kernel<<<1, 1, 0, st>>>(out_len, status, bad_segment);
+        HC_CK(hipGetLastError());
+        return HC_OK;
+    }
+    AppSizes s;
+    const int rc = app_sizes(*info, in_len, add_len, dec_in, s);
+    if (rc) return rc;
+    const AppWs w = app_ws(work, s);
+    if (work_bytes < w.total) return HC_ERR_ARG;
+    const uint64_t C = s.p.coded, D = s.p.decoded;
+    const AppCall a{in, out, in_len, out_cap, skip,
+                    get64(kMagic), info->flags & 0xFFFFu, info->raw_len, info->seg_bytes, info->width, c.n,
+                    c.full, c.last, info->raw_len + add_len, s.p.nc.n, s.p.nc.last,
+                    s.p.K, C, D, s.p.tail, add_len, s.slot_full, s.cap_full, s.cap_last,
+                    s.check ? 1u : 0u, gather ? 1u : 0u, w, out_len, bad_segment, status};
+
+    seg_aopen_kernel<<<1, kScan, 0, st>>>(a);
+    HC_CK(hipGetLastError());
+    if (D) {
+        Batch b{in, w.d_in_off, w.d_in_len, 1, w.stage, w.d_out_off, w.d_out_cap, w.d_out_len, w.d_status, 0};
+        if (s.adapt) HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
+        else HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
+        if (s.check)
+            HC_CK(hc::launch_crc32(w.stage, w.d_out_off, w.d_out_cap, 1, w.d_crc, hc::CrcGate{w.d_status, w.d_out_len}, st));
+    }
+    if (C) {
+        seg_aplan_kernel<<<(uint32_t)((C + 255) / 256), 256, 0, st>>>(a);
+        HC_CK(hipGetLastError());
+        // the added bytes behind the open tail, one range per coded entry, at any byte alignment
+        HC_CK(hc::launch_pack(add, w.pk_src, w.pk_len, (uint32_t)C, w.stage, w.pk_dst, st));
+        Batch b{w.stage, w.in_offs, w.in_lens, (uint32_t)C, w.slots, w.slot_offs, w.slot_caps, w.enc_lens, w.status,
+                info->flags & HC_FLAG_DIFF};
+        if (s.check) HC_CK(hc::launch_crc32(w.stage, w.in_offs, w.in_lens, C, w.crc, hc::CrcGate{nullptr, nullptr}, st));
+        if (s.adapt) HC_CK(hc::adapt_encode_batch(b, w.widths, w.awork, w.awork_bytes, st));
+        else HC_CK(hc::launch_encode(b, (info->flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
+    }
+    seg_aseal_kernel<<<1, kScan, 0, st>>>(a);
+    // the range write's splice over the seal's pieces (it reads these fields alone); the grid by the
+    // longest result there can be
+    UpdCall u{};
+    u.in = in;
+    u.out = out;
+    u.C = C;
+    u.w.pc_src = w.pc_src;
+    u.w.pc_dst = w.pc_dst;
+    u.w.pc_len = w.pc_len;
+    u.w.ctl = w.ctl;
+    u.w.slots = w.slots;
+    const uint64_t longest = gather ? s.slot_bytes : hc_seg_index::append_bound(s.p, in_len, c.n, s.check, s.slot_bytes);
+    const uint64_t tiles = longest / (4096ull * kSpliceChunks) + 1;
+    seg_usplice_kernel<<<(uint32_t)(tiles < 4096 ? tiles : 4096), 256, 0, st>>>(u);  // (the rest by stride)
+    if (!gather) {
+        const uint64_t blocks = (s.p.nc.n + 255) / 256;
+        seg_aindex_kernel<<<(uint32_t)(blocks < 65536 ? blocks : 65536), 256, 0, st>>>(a);
+    }
+    HC_CK(hipGetLastError());
+    return HC_OK;
+}
+
 // the host batch calls' sub-batch limit, as hc_pipe.hip reads it
 uint64_t pipe_bytes()
 {
@@ -1785,6 +2193,136 @@ int hc_seg_update(const uint8_t *in, uint64_t in_len, const hc_seg_patch_t *patc
     if (bad_segment) *bad_segment = h[2];
     if (status) return status;
     if (h[0]) HC_CK(hipMemcpy(out, dout.p, h[0], hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_seg_append_plan(const hc_seg_info_t *info, uint64_t in_len, uint64_t add_len, hc_seg_info_t *new_info,
+                       uint64_t *first_coded, uint64_t *n_decoded)
+{
+    if (!info || !new_info || !first_coded || !n_decoded) return HC_ERR_ARG;
+    Cuts c;
+    if (!info_ok(*info, in_len, c)) return HC_ERR_ARG;
+    AppPlan p;
+    const int rc = hc_seg_index::append_plan(c, info->raw_len, add_len, info->seg_bytes,
+                                             (info->flags & HC_FLAG_ADAPT) != 0, info->width, &p);
+    if (rc) return rc;
+    *new_info = *info;
+    new_info->raw_len = info->raw_len + add_len;
+    new_info->n_segments = p.nc.n;
+    *first_coded = p.K;
+    *n_decoded = p.decoded;
+    return HC_OK;
+}
+
+uint64_t hc_seg_append_bound(const hc_seg_info_t *info, uint64_t in_len, uint64_t add_len)
+{
+    if (!info) return 0;
+    Cuts c;
+    AppSizes s;
+    if (!info_ok(*info, in_len, c) || app_sizes(*info, in_len, add_len, nullptr, s) != HC_OK) return 0;
+    return hc_seg_index::append_bound(s.p, in_len, c.n, s.check, s.slot_bytes);
+}
+
+uint64_t hc_seg_append_work_bound(const hc_seg_info_t *info, uint64_t in_len, uint64_t add_len)
+{
+    if (!info) return 0;
+    Cuts c;
+    if (!info_ok(*info, in_len, c)) return 16;  // rejected without a workspace
+    AppSizes s;
+    if (app_sizes(*info, in_len, add_len, nullptr, s) != HC_OK) return 0;
+    return app_ws(nullptr, s).total;
+}
+
+int hc_seg_append_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, const uint8_t *add,
+                      uint64_t add_len, uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status,
+                      uint64_t *bad_segment, void *work, uint64_t work_bytes, void *stream)
+{
+    return append_dev(in, in_len, info, add, add_len, out, out_cap, out_len, status, bad_segment, work, work_bytes,
+                      stream, false, 0, nullptr);
+}
+
+int hc_seg_append(const uint8_t *in, uint64_t in_len, const uint8_t *add, uint64_t add_len, uint8_t *out,
+                  uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment)
+{
+    if ((!in && in_len) || !out_len || (!out && out_cap) || (!add && add_len)) return HC_ERR_ARG;
+    auto fail = [&](int rc, uint64_t len) {
+        *out_len = len;
+        if (bad_segment) *bad_segment = kNoSeg;
+        return rc;
+    };
+    hc_seg_info_t info;
+    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0);
+    AppSizes s;
+    {
+        const int rc = app_sizes(info, in_len, add_len, nullptr, s);
+        if (rc) return rc;
+    }
+    // The index on the host: the verdict without a device, and the kept block's last byte. Old segment
+    // n - 1, when it is not kept, starts at the next multiple of 16 and ends with the container.
+    const uint64_t n = s.c.n, K = s.p.K, C = s.p.coded;
+    const uint64_t first = align16(index_end(n, s.check)), new_first = align16(index_end(s.p.nc.n, s.check));
+    uint64_t s0 = 0, kept_end = 0;
+    if (hc_seg_index::index_scan(in, in_len, n, s.check, K ? Cover{K - 1, 1} : Cover{0, 0}, &s0, &kept_end) != HC_OK)
+        return fail(HC_ERR_SEG_HEADER, 0);
+    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0);
+    if (K == 0) kept_end = first;
+    const uint64_t kept_len = kept_end - first;
+    if (C == 0) {  // nothing is added: the input container
+        if (in_len > out_cap) return fail(HC_ERR_CAPACITY, in_len);
+        memcpy(out, in, in_len);
+        return fail(HC_OK, in_len);
+    }
+    (void)fail(HC_OK, 0);  // (what a HIP error below leaves behind)
+    // The compact upload: header and index [0, first), then old segment n - 1's stream when it is
+    // decoded; in_len stays the container's. The kept bytes never leave the host.
+    const uint64_t last_off = K == n ? in_len : align16(kept_end);
+    const uint64_t dec_in = s.p.decoded ? in_len - last_off : 0;
+    {
+        const int rc = app_sizes(info, in_len, add_len, &dec_in, s);  // the decoder's workspace by the stream's own length
+        if (rc) return rc;
+    }
+    const uint64_t wb = app_ws(nullptr, s).total;
+    hipStream_t st = nullptr;
+    DevBuf din, dadd, dout, work, meta;
+    HC_CK(din.alloc(first + dec_in + 16));
+    HC_CK(dadd.alloc(add_len + 16));
+    HC_CK(dout.alloc(s.slot_bytes + 16));
+    HC_CK(work.alloc(wb));
+    HC_CK(meta.alloc(32));
+    HC_CK(hipMemcpyAsync(din.p, in, first, hipMemcpyHostToDevice, st));
+    if (dec_in) HC_CK(hipMemcpyAsync(din.as<uint8_t>() + first, in + last_off, dec_in, hipMemcpyHostToDevice, st));
+    HC_CK(hipMemcpyAsync(dadd.p, add, add_len, hipMemcpyHostToDevice, st));
+    uint64_t *m = meta.as<uint64_t>();
+    const int rc = append_dev(din.as<uint8_t>(), in_len, &info, dadd.as<uint8_t>(), add_len, dout.as<uint8_t>(), out_cap, m,
+                              reinterpret_cast<int32_t *>(m + 1), m + 2, work.p, wb, st, true, last_off - first, &dec_in);
+    if (rc) return rc;
+    uint64_t h[4] = {0, 0, 0, 0};
+    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    HC_CK(hipStreamSynchronize(st));
+    const int status = (int32_t)(uint32_t)h[1];
+    *out_len = h[0];
+    if (bad_segment) *bad_segment = h[2];
+    if (status) return status;
+    // the result on the host: header, index, the kept block from `in`, the coded streams as gathered
+    const AppWs w = app_ws(work.p, s);
+    const uint64_t new_n = s.p.nc.n, base = new_first + align16(kept_len), gathered = h[0] - base;
+    std::vector<uint64_t> lens(C);
+    std::vector<uint32_t> crcs(s.check ? C : 0);
+    HC_CK(hipMemcpyAsync(lens.data(), w.enc_lens, 8 * C, hipMemcpyDeviceToHost, st));
+    if (s.check) HC_CK(hipMemcpyAsync(crcs.data(), w.crc, 4 * C, hipMemcpyDeviceToHost, st));
+    HC_CK(hipMemcpyAsync(out + base, dout.p, gathered, hipMemcpyDeviceToHost, st));
+    memcpy(out, in, 16);
+    const uint64_t words[4] = {info.raw_len + add_len, info.seg_bytes, info.width, new_n};
+    memcpy(out + 16, words, 32);
+    memcpy(out + 48, in + 48, 8 * K);
+    if (s.check) memcpy(out + 48 + 8 * new_n, in + 48 + 8 * n, 4 * K);
+    const uint64_t idx_end = index_end(new_n, s.check);
+    memset(out + idx_end, 0, new_first - idx_end);
+    memcpy(out + new_first, in + first, kept_len);
+    memset(out + new_first + kept_len, 0, base - (new_first + kept_len));
+    HC_CK(hipStreamSynchronize(st));
+    memcpy(out + 48 + 8 * K, lens.data(), 8 * C);
+    if (s.check) memcpy(out + 48 + 8 * new_n + 4 * K, crcs.data(), 4 * C);
     return HC_OK;
 }
 

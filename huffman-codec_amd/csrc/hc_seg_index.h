@@ -228,4 +228,62 @@ inline UpdPlan update_plan(const Cuts &c, uint64_t raw, const hc_seg_patch_t *p,
     return u;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Append (hc_seg_append*): the host's plan of raw bytes added behind a container. The cuts of
+// raw + add agree with the old ones on every segment below the old last one, and on that one too
+// when it already had the shape of a cut that is not the last. Segments 0 .. K - 1 are kept; the
+// coded segments K .. n' - 1 hold raw bytes [K full, raw + add): the open tail [K full, raw), then
+// the added bytes. Coded entry c (segment K + c) has its raw bytes at c full of a staging region.
+// ---------------------------------------------------------------------------------------------
+inline uint64_t sat_mul(uint64_t a, uint64_t b) { return b && a > ~0ull / b ? ~0ull : a * b; }
+struct AppPlan {
+    Cuts nc;            // the cuts of raw + add (full is the old one)
+    uint64_t K, coded;  // the first coded segment; n' - K
+    uint64_t decoded;   // 1: old segment n - 1 is decoded first (K == n - 1 and it is not empty)
+    uint64_t tail;      // the open tail's bytes: raw - K full, and none when K == n
+    uint64_t stage;     // tail + add: the raw bytes of the coded segments
+};
+// c: the cuts of raw (from info_ok). HC_OK, HC_ERR_ARG (raw + add wraps) or HC_ERR_MATRIX_SIZE (an
+// adaptive container and add is no multiple of width).
+inline int append_plan(const Cuts &c, uint64_t raw, uint64_t add, uint64_t seg, bool adapt, uint64_t width, AppPlan *p)
+{
+    memset(p, 0, sizeof(*p));
+    if (raw + add < raw) return HC_ERR_ARG;
+    if (adapt && add % width != 0) return HC_ERR_MATRIX_SIZE;
+    p->nc = seg_cuts(raw + add, seg, adapt, width);  // valid: raw's cuts are, and rows are only added
+    // n' >= n. Old cut n - 1 is new cut n - 1 when the new one is no longer the last and the old
+    // one was a full cut; with n' == n the last cut grew by add.
+    p->K = (add == 0 || (p->nc.n > c.n && c.last == c.full)) ? c.n : c.n - 1;
+    p->coded = p->nc.n - p->K;
+    p->decoded = (p->K == c.n - 1 && c.last > 0) ? 1 : 0;
+    p->tail = p->K == c.n ? 0 : raw - p->K * c.full;  // (K == n: empty, and with add == 0 n full may pass raw)
+    p->stage = p->tail + add;
+    return HC_OK;
+}
+// the length of coded entry e's cut
+inline uint64_t append_cut(const AppPlan &p, uint64_t e) { return e == p.coded - 1 ? p.nc.last : p.nc.full; }
+// S: the sum of align16(bound(cut)) over the coded segments. bound_full, bound_last:
+// align16(hc_compress_bound) of a full cut and of the new last one.
+inline uint64_t append_slots(const AppPlan &p, uint64_t bound_full, uint64_t bound_last)
+{
+    return p.coded ? sat_add(sat_mul(p.coded - 1, bound_full), bound_last) : 0;
+}
+// hc_seg_append_bound: in_len, the index's growth, the kept block's padding, the slots
+inline uint64_t append_bound(const AppPlan &p, uint64_t in_len, uint64_t old_n, bool check, uint64_t slots)
+{
+    const uint64_t grow = align16(sat_mul(check ? 12 : 8, p.nc.n - old_n));
+    return sat_add(sat_add(in_len, grow), sat_add(16, slots));
+}
+// hc_seg_append_work_bound without the adaptive workspace (C = coded): 9 arrays of 8 C bytes, the
+// status (and crc) words, 2 C + 1 copy pieces, the one decoder entry (96 bytes; checked: 112), 64 of
+// control words, the staging region and the slots. For C <= 2^31 - 1 (the calls refuse more).
+inline uint64_t append_work_base(const AppPlan &p, bool check, uint64_t slots)
+{
+    const uint64_t C = p.coded;
+    if (p.stage > ~0ull - 15) return ~0ull;
+    uint64_t t = 9 * align16(8 * C) + align16(4 * C) + (check ? align16(4 * C) : 0) + 3 * align16(8 * (2 * C + 1));
+    t += (check ? 112 : 96) + 64;
+    return sat_add(sat_add(t, align16(p.stage)), slots);
+}
+
 }  // namespace hc_seg_index

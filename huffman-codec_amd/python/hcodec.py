@@ -181,6 +181,13 @@ def _load(path):
                                     vp, u64, vp]
     L.hc_seg_update.argtypes = [u8p, u64, pp, ctypes.c_uint32, u8p, u64, u8p, u64, ctypes.POINTER(u64),
                                 ctypes.POINTER(u64)]
+    L.hc_seg_append_plan.argtypes = [ctypes.POINTER(SegInfo), u64, u64, ctypes.POINTER(SegInfo), ctypes.POINTER(u64),
+                                     ctypes.POINTER(u64)]
+    for f in (L.hc_seg_append_bound, L.hc_seg_append_work_bound):
+        f.argtypes = [ctypes.POINTER(SegInfo), u64, u64]
+        f.restype = u64
+    L.hc_seg_append_dev.argtypes = [vp, u64, ctypes.POINTER(SegInfo), vp, u64, vp, u64, vp, vp, vp, vp, u64, vp]
+    L.hc_seg_append.argtypes = [u8p, u64, u8p, u64, u8p, u64, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.hc_seg_compress_batch_work_bound.argtypes = [ctypes.POINTER(SegEncItem), ctypes.c_uint32, ctypes.c_uint32, u64]
     L.hc_seg_compress_batch_work_bound.restype = u64
     L.hc_seg_compress_batch_dev.argtypes = [vp, vp, ctypes.POINTER(SegEncItem), ctypes.c_uint32, ctypes.c_uint32, u64,
@@ -634,6 +641,80 @@ def seg_update_dev(inp, patches, patch_data, out, out_len, status, bad_segment=N
                                  _dp(work), work.numel(), _stream_handle(stream))
     if rc:
         raise HCodecError(f"hc_seg_update_dev failed: {rc}")
+    return work
+
+
+def seg_append_plan(info, in_len, add_len):
+    """hc_seg_append_plan (host only, no device): (status, the result's SegInfo or None, the first
+    coded segment K, the decoded segments: 0 or 1) of add_len bytes appended to a container"""
+    new = SegInfo()
+    k = ctypes.c_uint64(0)
+    dec = ctypes.c_uint64(0)
+    st = lib().hc_seg_append_plan(ctypes.byref(info) if info is not None else None, in_len, add_len, ctypes.byref(new),
+                                  ctypes.byref(k), ctypes.byref(dec))
+    return st, (new if st == 0 else None), k.value, dec.value
+
+
+def seg_append_bound(info, in_len, add_len):
+    """hc_seg_append_bound: an output capacity that always suffices (0: the call refuses the arguments)"""
+    return int(lib().hc_seg_append_bound(ctypes.byref(info) if info is not None else None, in_len, add_len))
+
+
+def seg_append_work_bound(info, in_len, add_len):
+    """hc_seg_append_work_bound: the device call's workspace (0: refused; 16: an info that fails)"""
+    return int(lib().hc_seg_append_work_bound(ctypes.byref(info) if info is not None else None, in_len, add_len))
+
+
+def seg_append(data, add, full=False, cap=None):
+    """hc_seg_append: (status, the container of the raw bytes of `data` followed by `add`); full:
+    (status, bytes, out_len, bad_segment). cap: the output capacity (default: hc_seg_append_bound)."""
+    b, p = _buf(data)
+    ab, ap = _buf(add)
+    if cap is None:
+        st, info = seg_info(b)
+        cap = seg_append_bound(info, len(b), len(ab)) if st == 0 else 0
+    out = ctypes.create_string_buffer(max(int(cap), 1))
+    n = ctypes.c_uint64(0)
+    bad = ctypes.c_uint64(NO_SEGMENT)
+    st = lib().hc_seg_append(p, len(b), ap, len(ab), ctypes.cast(out, ctypes.c_void_p), cap, ctypes.byref(n),
+                             ctypes.byref(bad))
+    got = out.raw[:n.value] if st == 0 else b""
+    return (st, got, n.value, bad.value) if full else (st, got)
+
+
+def seg_append_dev(inp, add, out, out_len, status, bad_segment=None, info=None, stream=None, work=None, in_len=None,
+                   out_cap=None, add_len=None):
+    """hc_seg_append_dev on CUDA tensors: the container in inp[:in_len] with add[:add_len] (a uint8
+    tensor at any alignment) appended to its raw bytes, into `out` (capacity out_cap, default all of
+    it). info as for seg_decompress_dev. Arguments that the call refuses raise. Returns the workspace."""
+    _check_seg(inp, out, out_len, status, bad_segment)
+    import torch
+    if not isinstance(add, torch.Tensor) or add.dtype != torch.uint8 or not add.is_contiguous() \
+            or add.device != inp.device:
+        raise TypeError("add: expected a contiguous uint8 tensor on the input's device")
+    n = inp.numel() if in_len is None else int(in_len)
+    if n > inp.numel():
+        raise ValueError(f"in_len {n} exceeds the {inp.numel()}-byte input tensor")
+    cap = out.numel() if out_cap is None else int(out_cap)
+    if cap > out.numel():
+        raise ValueError(f"out_cap {cap} exceeds the {out.numel()}-byte output tensor")
+    m = add.numel() if add_len is None else int(add_len)
+    if m > add.numel():
+        raise ValueError(f"add_len {m} exceeds the {add.numel()}-byte tensor")
+    if info is None:
+        head, p = _buf(inp[:min(n, 48)].cpu().numpy().tobytes())
+        info = SegInfo()  # stays all zero when the header does not parse: the call rejects it
+        lib().hc_seg_info(p, n, ctypes.byref(info))
+    need = int(lib().hc_seg_append_work_bound(ctypes.byref(info), n, m))
+    if work is None:
+        work = _work(need, inp.device)
+    _check_work(work, inp.device, need)
+    rc = lib().hc_seg_append_dev(_dp(inp), n, ctypes.byref(info), _dp(add) if m else ctypes.c_void_p(None), m,
+                                 _dp(out), cap, _dp(out_len), _dp(status),
+                                 ctypes.c_void_p(None) if bad_segment is None else _dp(bad_segment),
+                                 _dp(work), work.numel(), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_seg_append_dev failed: {rc}")
     return work
 
 

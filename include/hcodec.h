@@ -372,7 +372,7 @@ int hc_seg_decompress_range_dev(const uint8_t *in, uint64_t in_len, const hc_seg
  * Segment k is the stream hc_compress writes for segment k's bytes alone and the cuts are a
  * function of the header, so a write that keeps raw_len keeps n, the header and the index size:
  * only the segments that the new bytes touch are coded again, and every other stream is carried
- * over byte for byte. raw_len never changes (no append, no truncation).
+ * over byte for byte. raw_len never changes (no truncation; appending is hc_seg_append's).
  *
  * Patches. A call takes a list: patch i makes raw bytes [offset, offset + length) of the container
  * patch_data[src_off .. src_off + length). `patches` is HOST memory, read before the call returns
@@ -471,6 +471,115 @@ int hc_seg_update_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *i
  * NULL. */
 int hc_seg_update(const uint8_t *in, uint64_t in_len, const hc_seg_patch_t *patches, uint32_t n_patches,
                   const uint8_t *patch_data, uint64_t patch_data_len,
+                  uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment);
+
+/* ---------------------------------------------------------------------------------------
+ * Append: the container of X followed by T from the container of X, without recoding the rest. The cuts are
+ * a function of raw_len, seg_bytes, flags and width, every segment restarts the coder's model and
+ * segment k is the stream hc_compress writes for its cut alone: so when bytes are appended, every
+ * segment below the old last one keeps its cut and its stream, at most one old segment (the partly
+ * filled last one) is decoded, and only that one and the new ones are coded.
+ *
+ * Notation. n, full, last: the old container's cuts; R its raw_len; T the appended bytes, A their
+ * length; R' = R + A; n', last': the cuts of R' with the same seg_bytes, flags and width (full does
+ * not change, and n' >= n).
+ *
+ * First coded segment K. K = n when A == 0, and when old cut n - 1 equals new cut n - 1, i.e. the
+ * last segment was already a complete cut of the shape of one that is not the last (plain: R a
+ * non-zero multiple of seg_bytes; adaptive: the last band has exactly `rows` rows and at least 8
+ * rows are appended). Otherwise K = n - 1.
+ *
+ * Segments 0 .. K - 1 are kept: their streams are neither decoded nor checked, so a damaged kept
+ * segment is not noticed, as in a ranged read. Segments K .. n' - 1 are coded: they hold raw bytes
+ * [K full, R'), the old open tail [K full, R) followed by T. The open tail is empty when K == n. An
+ * adaptive open tail can be longer than `full` and end up in two new segments (width 16, seg_bytes
+ * 128, 19 rows + 5 rows: the old last band of 11 rows becomes bands of 8 and 8), and it can be the
+ * whole container (15 rows + 1 row: one segment becomes two).
+ *
+ * Decoded segment. When K == n - 1 and last > 0, old segment n - 1 is decoded whole first, and
+ * judged by hc_seg_decompress's mapping: the coder's own status; another length than its cut:
+ * HC_ERR_SEG_SIZE; in a checked container the right length with another CRC-32: HC_ERR_SEG_CHECK.
+ * The empty segment of an empty container (last == 0) is not read or decoded.
+ *
+ * Arguments decided on the host: R + A wraps: HC_ERR_ARG; an adaptive container and A no multiple
+ * of width: HC_ERR_MATRIX_SIZE; more than 2^31 - 1 coded segments (counted once the other two
+ * pass): HC_ERR_ARG. A == 0 is valid: the result is the input container, byte for byte.
+ *
+ * Result. out[0 .. *out_len) is: the 48 header bytes with raw_len = R' and n_segments = n';
+ * enc_len[0 .. K) copied and enc_len[K .. n') new; in a checked container crc[0 .. K) copied to
+ * their new place at 48 + 8 n' and crc[K .. n') the CRC-32 of the new cuts' raw bytes; zero padding
+ * up to align16 of the index end; the old bytes from segment 0's first byte to segment K - 1's
+ * last, copied verbatim as one block (old padding between kept segments included; the block moves
+ * by a multiple of 16); then every coded segment at the next multiple of 16, with zero padding
+ * after the kept block and after every coded segment but the last. For a container that this
+ * library wrote from raw bytes X that is byte for byte what hc_seg_compress2 gives for X followed by T with
+ * the same flags (check bit included), width and seg_bytes.
+ *
+ * Status, in this order (host call):
+ *   1  HC_ERR_ARG         null pointers (device call: in, out or work not 16-byte aligned; [in,
+ *                         in + in_len) and [out, out + out_cap) overlap)    *out_len, *bad_segment not set
+ *   2  HC_ERR_SEG_HEADER  the header fails                                   0, UINT64_MAX
+ *   3  HC_ERR_ARG, HC_ERR_MATRIX_SIZE  the argument rules above (device call: work_bytes below the
+ *                         bound)                                             not set
+ *   4  HC_ERR_SEG_HEADER  the index fails: all n entries are scanned and must tile the container
+ *                         exactly, for every A, 0 included                   0, UINT64_MAX
+ *   5  HC_ERR_DEVICE      host call without a device                         0, UINT64_MAX
+ *   6  the decoded segment's failing status, by the mapping above            0, n - 1
+ *   7  HC_ERR_CAPACITY    the result is longer than out_cap                  the length needed, UINT64_MAX
+ *   8  HC_OK                                                                 the new length, UINT64_MAX
+ * Row 6 comes before row 7, as in hc_seg_update, for the same reason.
+ *
+ * Writes. No byte outside out[0 .. out_cap) is written, whatever the status, and on a non-zero
+ * status no byte of out is written at all.
+ * ------------------------------------------------------------------------------------- */
+
+/* Host only, no device. *new_info: the header of the result (raw_len and n_segments new);
+ * *first_coded = K; *n_decoded: 0 or 1. HC_OK, HC_ERR_ARG (a null pointer, an info that fails
+ * hc_seg_info's rules for in_len, R + A wraps) or HC_ERR_MATRIX_SIZE. */
+int hc_seg_append_plan(const hc_seg_info_t *info, uint64_t in_len, uint64_t add_len,
+                       hc_seg_info_t *new_info, uint64_t *first_coded, uint64_t *n_decoded);
+/* An out_cap that always suffices: in_len + a16((8, checked: 12) (n' - n)) + 16 + S, with S the sum
+ * of a16(hc_compress_bound(cut, adaptive)) over the coded segments. 0 for arguments that the call
+ * refuses. */
+uint64_t hc_seg_append_bound(const hc_seg_info_t *info, uint64_t in_len, uint64_t add_len);
+/* The device call's workspace. With C = n' - K the coded segments, D the decoded one (0 or 1), S as
+ * above and a16(x) = x rounded up to a multiple of 16:
+ *   9 a16(8 C) + a16(4 C) + 3 a16(8 (2 C + 1)) + 160 [+ a16(4 C) + 16 checked]
+ *   + a16(O + A) + S, O the open tail's bytes (R - K full; 0 when K == n)
+ *   [+ a16(max(hc_adapt_compress_work_bound(O + A, C) if C > 0,
+ *              hc_adapt_decompress_work_bound(min(in_len, hc_compress_bound(last, 1)), last, 1) if D > 0))
+ *      adaptive]
+ * It grows with the open tail and with A, never with n or with the kept bytes. (The adaptive
+ * decoder's part is sized by the longest stream this library writes for the decoded cut. A forged
+ * stream that announces more symbols than fit it fails as HC_ERR_SEG_SIZE.) 0 for a null info or
+ * arguments that the call refuses; 16 for an info that fails hc_seg_info's rules (as
+ * hc_seg_update_work_bound). */
+uint64_t hc_seg_append_work_bound(const hc_seg_info_t *info, uint64_t in_len, uint64_t add_len);
+
+/* Device buffers, asynchronous on `stream`, under the rules of hc_seg_update_dev: in, out and work
+ * 16-byte aligned; out_len, status and bad_segment (may be NULL) DEVICE pointers; no device
+ * allocation, no host synchronisation, no host read of device memory, every byte of scratch from
+ * `work`; capturable in a graph. `add` is a DEVICE pointer of any byte alignment. Rows 1 and 3 are
+ * the return value; an info that fails hc_seg_info's rules gives HC_ERR_SEG_HEADER as the device
+ * status with return value HC_OK; everything else is the device status.
+ *
+ * The coded segments' raw bytes lie in a staging region of `work`: the decoded segment decodes to
+ * its start, one pack launch lays T behind it (one range per coded segment), and one encode launch
+ * codes them into bound-sized slots. The new container is then spliced from the kept block and the
+ * slots, 16 bytes per lane, and the new index is written in front of them. */
+int hc_seg_append_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info,
+                      const uint8_t *add, uint64_t add_len, uint8_t *out, uint64_t out_cap,
+                      uint64_t *out_len, int32_t *status, uint64_t *bad_segment,
+                      void *work, uint64_t work_bytes, void *stream);
+
+/* Host buffers, synchronous. The header, the arguments and the index are checked on the host (rows
+ * 2 - 4 need no device). The kept bytes never cross to the device: only the header, the index, the
+ * decoded segment's stream and T are uploaded; the same stages run on the cached scratch of the
+ * single calls; the verdict, the coded segments' index words and their streams, gathered back to
+ * back, come down, and the result is put together on the host with the kept block taken from `in`.
+ * Device memory and transfers grow with the index, the open tail and A, not with the kept bytes.
+ * bad_segment may be NULL. */
+int hc_seg_append(const uint8_t *in, uint64_t in_len, const uint8_t *add, uint64_t add_len,
                   uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment);
 
 /* ---------------------------------------------------------------------------------------
