@@ -79,6 +79,26 @@ using hc_seg_index::seg_cuts;
 // ---------------------------------------------------------------------------------------------
 // Workspace layouts (host-side carving; every region 16-byte aligned)
 // ---------------------------------------------------------------------------------------------
+// hands out the regions of a workspace one after the other, from `from` on
+struct Carver {
+    uint8_t *p;  // null: sizing only
+    uint64_t o;
+    explicit Carver(void *work, uint64_t from = 0) : p(static_cast<uint8_t *>(work)), o(from) {}
+    uint8_t *take(uint64_t bytes)
+    {
+        uint8_t *q = p ? p + o : nullptr;
+        o += align16(bytes);
+        return q;
+    }
+    template <class T>
+    T *arr(uint64_t n)
+    {
+        return reinterpret_cast<T *>(take(sizeof(T) * n));
+    }
+    uint64_t *take64(uint64_t n) { return arr<uint64_t>(n); }
+    uint64_t total() const { return o; }
+};
+
 struct EncWs {
     uint64_t *in_offs, *in_lens, *widths, *out_offs, *out_caps, *out_lens, *dst_offs;
     int32_t *status;
@@ -91,27 +111,21 @@ struct EncWs {
 EncWs carve_enc(void *work, uint64_t n, uint64_t slot_bytes, uint64_t awork_bytes, bool check)
 {
     EncWs w;
-    uint8_t *p = static_cast<uint8_t *>(work);
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p ? p + o : nullptr;  // null: sizing only
-        o += align16(bytes);
-        return q;
-    };
-    w.in_offs = reinterpret_cast<uint64_t *>(take(8 * n));
-    w.in_lens = reinterpret_cast<uint64_t *>(take(8 * n));
-    w.widths = reinterpret_cast<uint64_t *>(take(8 * n));
-    w.out_offs = reinterpret_cast<uint64_t *>(take(8 * n));
-    w.out_caps = reinterpret_cast<uint64_t *>(take(8 * n));
-    w.out_lens = reinterpret_cast<uint64_t *>(take(8 * n));
-    w.dst_offs = reinterpret_cast<uint64_t *>(take(8 * n));
-    w.status = reinterpret_cast<int32_t *>(take(4 * n));
-    w.crc = reinterpret_cast<uint32_t *>(take(check ? 4 * n : 0));
-    w.ctl = reinterpret_cast<uint64_t *>(take(16));
-    w.slots = take(slot_bytes);
-    w.awork = take(awork_bytes);
+    Carver cv(work);
+    w.in_offs = cv.take64(n);
+    w.in_lens = cv.take64(n);
+    w.widths = cv.take64(n);
+    w.out_offs = cv.take64(n);
+    w.out_caps = cv.take64(n);
+    w.out_lens = cv.take64(n);
+    w.dst_offs = cv.take64(n);
+    w.status = cv.arr<int32_t>(n);
+    w.crc = cv.arr<uint32_t>(check ? n : 0);
+    w.ctl = cv.take64(2);
+    w.slots = cv.take(slot_bytes);
+    w.awork = cv.take(awork_bytes);
     w.awork_bytes = awork_bytes;
-    w.total = o;
+    w.total = cv.total();
     return w;
 }
 
@@ -147,6 +161,78 @@ __device__ __forceinline__ uint64_t block_scan(uint64_t v, uint64_t *part, uint6
 }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// the six header words of a container, as the caller's host copy has them
+struct HeaderWords {
+    uint64_t magic, flags, raw_len, seg_bytes, width, n;
+};
+
+// The header and the index of the container at `in`, by the whole workgroup of kScan threads; the
+// open kernel of every operation is built on it. The host has checked its copy of the header
+// against in_len (48 + 8 n <= in_len among the rest; 12 n in a checked container, whose crc words
+// follow the lengths); here the device bytes must equal that copy, and the index must tile
+// [align16(48 + 8 n or 12 n), in_len) exactly. enc_len entries are untrusted: the offsets add with
+// saturation and every range is compared by subtraction, so a forged length cannot wrap into a
+// valid offset. each(k, off, len) runs for every segment that passes the range rules, with its
+// place in the container. Returns, to every thread, whether the header or any entry failed.
+template <class Each>
+__device__ __forceinline__ bool scan_index(const uint8_t *in, const HeaderWords &h, uint64_t in_len, bool check, Each each)
+{
+    __shared__ uint64_t part[kScan / 64];
+    __shared__ uint32_t s_err;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) s_err = 0;
+    __syncthreads();
+    bool err = false;
+    const uint64_t *i64 = reinterpret_cast<const uint64_t *>(in);
+    if (tid < 6) {
+        const uint64_t want = tid == 0 ? h.magic : tid == 1 ? h.flags : tid == 2 ? h.raw_len
+                              : tid == 3 ? h.seg_bytes : tid == 4 ? h.width : h.n;
+        if (i64[tid] != want) err = true;
+    }
+    uint64_t carry = align16(index_end(h.n, check));
+    for (uint64_t base = 0; base < h.n; base += kScan) {
+        const uint64_t k = base + tid;
+        const bool in_k = k < h.n;
+        const uint64_t len = in_k ? i64[6 + k] : 0;
+        const bool big = len > in_len;
+        uint64_t total;
+        const uint64_t off = sat_add(carry, block_scan(in_k && !big ? align16(len) : 0, part, total));
+        if (in_k) {
+            if (big || off > in_len || len > in_len - off) err = true;
+            else if (k == h.n - 1 && off + len != in_len) err = true;  // truncated, or trailing bytes
+            else each(k, off, len);
+        }
+        carry = sat_add(carry, total);
+    }
+    if (err) s_err = 1;
+    __syncthreads();
+    return s_err != 0;
+}
+
+// The lowest entry of [0, n) that `failed` names, by the workgroup's kScan threads: each takes
+// the entries of its stride and leaves its lowest in *s_bad by atomicMin. *s_bad is a word of LDS
+// that the caller sets to kNoSeg before a barrier and reads after the next one (kNoSeg: none).
+template <class Failed>
+__device__ __forceinline__ void lowest_failing(uint64_t n, unsigned long long *s_bad, Failed failed)
+{
+    uint64_t bad = kNoSeg;
+    for (uint64_t i = threadIdx.x; i < n && bad == kNoSeg; i += kScan)
+        if (failed(i)) bad = i;
+    if (bad != kNoSeg) atomicMin(s_bad, (unsigned long long)bad);
+}
+
+// The status of a decoded segment that failed (its coder did, or it decoded cleanly to another
+// length than its cut, or to that length with another checksum than the index has): the coder's
+// own, except HC_ERR_CAPACITY (it wanted more room than its cut) and a clean decode to fewer bytes,
+// which are HC_ERR_SEG_SIZE, and a clean decode to the cut's length, which only the checksum can
+// have failed.
+__device__ __forceinline__ int32_t decoded_verdict(int32_t st, uint64_t len, uint64_t cut)
+{
+    if (st == 0 && len == cut) return HC_ERR_SEG_CHECK;
+    if (st == 0 || st == HC_ERR_CAPACITY) return HC_ERR_SEG_SIZE;
+    return st;
+}
 
 // hc_seg_decompress_dev with an info that fails the host checks: the verdict alone
 __global__ void seg_reject_kernel(uint64_t *out_len, int32_t *status, uint64_t *bad_segment)
@@ -218,11 +304,29 @@ int host_status(uint64_t n, int use_adapt, uint64_t width)
     return HC_OK;
 }
 
+// what a synchronous call that the host decides leaves in its outputs: rc, with no segment to blame
+int fail(int rc, uint64_t len, uint64_t *out_len, uint64_t *bad_segment)
+{
+    *out_len = len;
+    if (bad_segment) *bad_segment = kNoSeg;
+    return rc;
+}
+// The verdict of a device call that wrote out_len, status and bad_segment to words 0, 1 and 2 of
+// `meta`, once the stream is through: the outputs, and the status (HC_ERR_DEVICE: the read failed)
+int read_verdict(const DevBuf &meta, hipStream_t st, uint64_t *out_len, uint64_t *bad_segment)
+{
+    uint64_t h[4] = {0, 0, 0, 0};
+    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    HC_CK(hipStreamSynchronize(st));
+    *out_len = h[0];
+    if (bad_segment) *bad_segment = h[2];
+    return (int32_t)(uint32_t)h[1];
+}
+
 int seg_decompress_host(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_cap, bool alloc,
                         uint8_t **out_alloc, uint64_t *out_len, uint64_t *bad_segment)
 {
-    if (bad_segment) *bad_segment = kNoSeg;
-    *out_len = 0;
+    (void)fail(HC_OK, 0, out_len, bad_segment);
     hc_seg_info_t info;
     if (hc_seg_info(in, in_len, &info) != HC_OK) return HC_ERR_SEG_HEADER;
     if (!hc_device_ok()) return HC_ERR_DEVICE;
@@ -240,19 +344,14 @@ int seg_decompress_host(const uint8_t *in, uint64_t in_len, uint8_t *out, uint64
     const int rc = hc_seg_decompress_dev(din.as<uint8_t>(), in_len, &info, dout.as<uint8_t>(), out_cap, m,
                                          reinterpret_cast<int32_t *>(m + 1), m + 2, work.p, wb, st);
     if (rc) return rc;
-    uint64_t h[4] = {0, 0, 0, 0};
-    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    HC_CK(hipStreamSynchronize(st));
-    const int status = (int32_t)(uint32_t)h[1];
-    *out_len = h[0];
-    if (bad_segment) *bad_segment = h[2];
+    const int status = read_verdict(meta, st, out_len, bad_segment);
     if (status) return status;
     if (alloc) {
-        out = static_cast<uint8_t *>(malloc(h[0] ? h[0] : 1));
+        out = static_cast<uint8_t *>(malloc(*out_len ? *out_len : 1));
         if (!out) return HC_ERR_DEVICE;
         *out_alloc = out;
     }
-    if (h[0]) HC_CK(hipMemcpy(out, dout.p, h[0], hipMemcpyDeviceToHost));
+    if (*out_len) HC_CK(hipMemcpy(out, dout.p, *out_len, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 
@@ -421,17 +520,11 @@ EncBatchWs carve_enc_batch(void *work, uint64_t n_items, uint64_t n, uint64_t sl
 {
     EncBatchWs w;
     w.s = carve_enc(work, n, slot_bytes, awork_bytes, check);
-    uint8_t *p = static_cast<uint8_t *>(work);
-    uint64_t o = w.s.total;
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p ? p + o : nullptr;
-        o += align16(bytes);
-        return q;
-    };
-    w.items = reinterpret_cast<EncItem *>(take(sizeof(EncItem) * n_items));
-    w.seg_item = reinterpret_cast<uint32_t *>(take(4 * n));
-    w.ctl = reinterpret_cast<uint64_t *>(take(8 * n_items));
-    w.total = o;
+    Carver cv(work, w.s.total);
+    w.items = cv.arr<EncItem>(n_items);
+    w.seg_item = cv.arr<uint32_t>(n);
+    w.ctl = cv.take64(n_items);
+    w.total = cv.total();
     return w;
 }
 
@@ -657,29 +750,23 @@ DecWs carve_dec(void *work, uint64_t count, uint64_t nslots, uint64_t slot_bytes
                 uint64_t crc_bytes, uint64_t ctl_bytes, uint64_t n_records)
 {
     DecWs w;
-    uint8_t *p = static_cast<uint8_t *>(work);
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p ? p + o : nullptr;  // null: sizing only
-        o += align16(bytes);
-        return q;
-    };
-    w.in_offs = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.in_lens = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.out_offs = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.out_caps = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.out_lens = reinterpret_cast<uint64_t *>(take(8 * count));
-    w.status = reinterpret_cast<int32_t *>(take(4 * count));
-    w.crc = reinterpret_cast<uint32_t *>(take(crc_bytes));
-    w.ctl = reinterpret_cast<uint64_t *>(take(ctl_bytes));
-    w.items = reinterpret_cast<DecItem *>(take(sizeof(DecItem) * n_records));
-    w.cp_src = reinterpret_cast<uint64_t *>(take(8 * nslots));
-    w.cp_len = reinterpret_cast<uint64_t *>(take(8 * nslots));
-    w.cp_dst = reinterpret_cast<uint64_t *>(take(8 * nslots));
-    w.slots = take(slot_bytes);
-    w.awork = take(awork_bytes);
+    Carver cv(work);
+    w.in_offs = cv.take64(count);
+    w.in_lens = cv.take64(count);
+    w.out_offs = cv.take64(count);
+    w.out_caps = cv.take64(count);
+    w.out_lens = cv.take64(count);
+    w.status = cv.arr<int32_t>(count);
+    w.crc = reinterpret_cast<uint32_t *>(cv.take(crc_bytes));
+    w.ctl = reinterpret_cast<uint64_t *>(cv.take(ctl_bytes));
+    w.items = cv.arr<DecItem>(n_records);
+    w.cp_src = cv.take64(nslots);
+    w.cp_len = cv.take64(nslots);
+    w.cp_dst = cv.take64(nslots);
+    w.slots = cv.take(slot_bytes);
+    w.awork = cv.take(awork_bytes);
     w.awork_bytes = awork_bytes;
-    w.total = o;
+    w.total = cv.total();
     return w;
 }
 
@@ -698,13 +785,11 @@ struct DecCall {
     int32_t *status;                    // per item
 };
 
-// Item blockIdx.x. The host has checked its copy of the header against in_len (48 + 8 n <= in_len
-// among the rest; 12 n in a checked container, whose crc words follow the lengths); here the
-// device bytes must equal that copy, and the index must tile [align16(48 + 8 n or 12 n), in_len)
-// exactly, whatever the range. enc_len entries are untrusted: the offsets add with saturation and
-// every range is compared by subtraction, so a forged length cannot wrap into a valid offset.
-// Segment arrays for the covered segments only (entry seg0 + k - k0; input offsets from the call's
-// `in`, outputs from the call's base), and the staged ones' copies from slot0 on (sources from the
+// Item blockIdx.x: scan_index's header compare and index scan, whatever the range, written out in
+// this one kernel because built on scan_index it spills more scalar registers than it does as it
+// stands (profiles/seg_write_resource_usage.txt); a change of the rules goes into both. Segment
+// arrays for the covered segments only (entry seg0 + k - k0; input offsets from the call's `in`,
+// outputs from the call's base), and the staged ones' copies from slot0 on (sources from the
 // slots' start, destinations from `out`).
 template <class Src>
 __global__ __launch_bounds__(kScan) void seg_open_kernel(Src items, DecCall a)
@@ -792,28 +877,20 @@ __global__ __launch_bounds__(kScan) void seg_close_kernel(Src items, DecCall a)
     if (tid == 0) s_bad = kNoSeg;
     __syncthreads();
     const int32_t top = (int32_t)a.ctl[item];
-    if (top == 0) {
-        // the lowest segment that failed, decoded cleanly to another length than its cut, or to
-        // that length with another checksum (crc[i] is written exactly for those that reach it)
-        uint64_t bad = kNoSeg;
-        for (uint64_t i = tid; i < count && bad == kNoSeg; i += kScan)
-            if (seg_status[i] != 0 || out_lens[i] != out_caps[i] || (crc && crc[i] != want_crc[i])) bad = i;
-        if (bad != kNoSeg) atomicMin(&s_bad, (unsigned long long)bad);
-    }
+    // the lowest segment that failed, decoded cleanly to another length than its cut, or to that
+    // length with another checksum (crc[i] is written exactly for those that reach it)
+    if (top == 0)
+        lowest_failing(count, &s_bad, [&](uint64_t i) {
+            return seg_status[i] != 0 || out_lens[i] != out_caps[i] || (crc && crc[i] != want_crc[i]);
+        });
     __syncthreads();
     if (tid != 0) return;
     const uint64_t bad = s_bad;
     int32_t st = top;
     uint64_t len = top == HC_ERR_CAPACITY ? length : 0;
     if (top == 0) {
-        if (bad != kNoSeg) {
-            st = seg_status[bad];
-            // 64: it wanted more room than its cut; 0: it decoded to fewer bytes, or to the wrong ones
-            if (st == 0 && out_lens[bad] == out_caps[bad]) st = HC_ERR_SEG_CHECK;
-            else if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
-        } else {
-            len = length;
-        }
+        if (bad != kNoSeg) st = decoded_verdict(seg_status[bad], out_lens[bad], out_caps[bad]);
+        else len = length;
     }
     a.status[item] = st;
     a.out_lens[item] = len;
@@ -1040,82 +1117,185 @@ int decode_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, ui
 //   upatch   the patch records, a chunk per launch as kernel arguments: the pack arrays and the
 //            decoded entries' covered entries
 //   uplan    covered entry c: its segment, its staging range, its slot
-//   uopen    one workgroup: header against the caller's copy, scan of the whole index, the old place
-//            of every covered segment, the decoder's arrays
-//   <decode launch over the decoded entries, into staging; checked containers: their CRC-32>
-//   <pack launch: every patch's bytes over the staging region>
-//   <checked containers: CRC-32 of the covered entries' new raw bytes; encode launch into the slots>
-//   useal    one workgroup: the verdict, and the pieces of the new container: 2 C + 1 of them, old
-//            block j (the old bytes between covered entries j - 1 and j; the first one holds the
-//            header and the index) at 2 j and covered entry j's slot at 2 j + 1, each at the next
-//            multiple of 16 after the one before
-//   usplice  the pieces to their places, 16 bytes per lane; gated by the verdict
+//   uopen    one workgroup: header against the caller's copy, scan of the whole index (scan_index),
+//            the old place of every covered segment, the decoder's arrays
+//   <decode_to_stage: decode launch over the decoded entries, into staging; checked containers:
+//    their CRC-32>
+//   <code_from_stage: pack launch, every patch's bytes over the staging region; checked
+//    containers: CRC-32 of the covered entries' new raw bytes; encode launch into the slots>
+//   useal    one workgroup: the verdict (seal_failed, seal_fits), and the pieces of the new
+//            container: 2 C + 1 of them, old block j (the old bytes between covered entries j - 1
+//            and j; the first one holds the header and the index) at 2 j and covered entry j's slot
+//            at 2 j + 1, each at the next multiple of 16 after the one before
+//   splice   the pieces to their places, 16 bytes per lane; gated by the verdict
 //   uindex   the covered segments' enc_len and crc words over the copied index; gated too
+//
+// The append below runs the same stages over its own coded entries: what the two keep per coded
+// entry, per decoded entry and per piece is one block of the workspace (CodedWs), and what they do
+// with it (the plan of an entry, the coder launches, the seal's verdict, the splice) is written
+// once, here.
 // ---------------------------------------------------------------------------------------------
 using hc_seg_index::PatchRec;
 using hc_seg_index::UpdPlan;
 constexpr uint32_t kPatchChunk = 48;  // patch records per descriptor launch
 constexpr uint32_t kSpliceChunks = 8;  // 16-byte chunks per lane and tile: a workgroup's tile is 32 KiB
 
-struct UpdWs {
-    PatchRec *recs;
-    uint64_t *pk_src, *pk_len, *pk_dst;                                             // per patch
-    uint64_t *d_cov, *d_in_offs, *d_in_lens, *d_out_offs, *d_out_caps, *d_out_lens;  // per decoded entry
-    int32_t *d_status;
-    uint32_t *d_crc;  // checked containers
-    uint64_t *cov_seg, *old_off, *old_len, *in_offs, *in_lens, *widths, *slot_offs, *slot_caps, *enc_lens;  // per covered entry
+// What a write call (the range write, the append) keeps of the C segments it codes, of the D among
+// them that it decodes first, and of the 2 C + 1 pieces its result is spliced from. Coded entry c
+// has its raw bytes at c full of the staging region and its new stream in a bound-sized slot.
+struct CodedWs {
+    uint64_t *in_offs, *in_lens, *widths, *slot_offs, *slot_caps, *enc_lens;  // per coded entry
     int32_t *status;
     uint32_t *crc;  // checked containers
     uint64_t *pc_src, *pc_dst, *pc_len;  // per piece
-    uint64_t *ctl;  // [0] 1: sealed, the splice may copy; [1] the new length; [2] uopen's verdict
+    uint64_t *d_in_offs, *d_in_lens, *d_out_offs, *d_out_caps, *d_out_lens;  // per decoded entry
+    int32_t *d_status;
+    uint32_t *d_crc;  // checked containers
+    // [0] 1: sealed, the splice may copy; [1] the spliced bytes' end; [2] the open kernel's verdict;
+    // from [3] on: the operation's own
+    uint64_t *ctl;
     uint8_t *stage, *slots;
     void *awork;
-    uint64_t awork_bytes, total;
+    uint64_t awork_bytes;
+};
+CodedWs carve_coded(Carver &cv, uint64_t C, uint64_t D, bool check, uint64_t ctl_words, uint64_t stage_bytes,
+                    uint64_t slot_bytes, uint64_t awork_bytes)
+{
+    CodedWs w;
+    w.in_offs = cv.take64(C);
+    w.in_lens = cv.take64(C);
+    w.widths = cv.take64(C);
+    w.slot_offs = cv.take64(C);
+    w.slot_caps = cv.take64(C);
+    w.enc_lens = cv.take64(C);
+    w.status = cv.arr<int32_t>(C);
+    w.crc = cv.arr<uint32_t>(check ? C : 0);
+    w.pc_src = cv.take64(2 * C + 1);
+    w.pc_dst = cv.take64(2 * C + 1);
+    w.pc_len = cv.take64(2 * C + 1);
+    w.d_in_offs = cv.take64(D);
+    w.d_in_lens = cv.take64(D);
+    w.d_out_offs = cv.take64(D);
+    w.d_out_caps = cv.take64(D);
+    w.d_out_lens = cv.take64(D);
+    w.d_status = cv.arr<int32_t>(D);
+    w.d_crc = cv.arr<uint32_t>(check ? D : 0);
+    w.ctl = cv.take64(ctl_words);
+    w.stage = cv.take(stage_bytes);
+    w.slots = cv.take(slot_bytes);
+    w.awork = cv.take(awork_bytes);
+    w.awork_bytes = awork_bytes;
+    return w;
+}
+
+// a write call's three outputs
+struct WriteOut {
+    uint64_t *out_len, *bad_segment;
+    int32_t *status;
+};
+
+// coded entry c: `len` raw bytes at in_off of the staging region, and `cap` bytes at slot_off of the slots
+__device__ __forceinline__ void plan_coded(const CodedWs &w, uint64_t c, uint64_t in_off, uint64_t len,
+                                           uint64_t width, uint64_t slot_off, uint64_t cap)
+{
+    w.in_offs[c] = in_off;
+    w.in_lens[c] = len;
+    w.widths[c] = width;
+    w.slot_offs[c] = slot_off;
+    w.slot_caps[c] = cap;
+    w.enc_lens[c] = 0;
+    w.status[c] = HC_ERR_DEVICE;  // overwritten by the encode launch
+}
+// decoded entry d: its stream in the old container (none when the open kernel failed: nothing of
+// the container is read), and its cut's place in the staging region
+__device__ __forceinline__ void plan_decoded(const CodedWs &w, uint64_t d, bool bad, uint64_t in_off,
+                                             uint64_t in_len, uint64_t out_off, uint64_t cut)
+{
+    w.d_in_offs[d] = bad ? 0 : in_off;
+    w.d_in_lens[d] = bad ? 0 : in_len;
+    w.d_out_offs[d] = out_off;
+    w.d_out_caps[d] = cut;
+    w.d_out_lens[d] = 0;
+    w.d_status[d] = HC_ERR_DEVICE;  // overwritten by the decode launch
+}
+
+// The verdict of a write call before its pieces, by the seal's whole workgroup: the open kernel's,
+// else that of the lowest failing decoded entry (seg_close_kernel's rules), else the own status of
+// the lowest failing coded entry (an encoder never fails in a bound-sized slot; if one does, the
+// call must not succeed). want_crc: the old index's crc words, read in a checked container alone;
+// seg_d(d), seg_c(c): the container's segment of a decoded, of a coded entry. True: the call
+// failed, its outputs say so, and nothing will be spliced.
+template <class SegD, class SegC>
+__device__ __forceinline__ bool seal_failed(const CodedWs &w, uint64_t D, uint64_t C, const uint32_t *want_crc,
+                                            const WriteOut &o, SegD seg_d, SegC seg_c)
+{
+    __shared__ unsigned long long s_dbad, s_ebad;
+    if (threadIdx.x == 0) s_dbad = s_ebad = kNoSeg;
+    __syncthreads();
+    const int32_t top = (int32_t)w.ctl[2];
+    if (top == 0) {
+        lowest_failing(D, &s_dbad, [&](uint64_t d) {
+            return w.d_status[d] != 0 || w.d_out_lens[d] != w.d_out_caps[d] ||
+                   (want_crc && w.d_crc[d] != want_crc[seg_d(d)]);
+        });
+        lowest_failing(C, &s_ebad, [&](uint64_t c) { return w.status[c] != 0; });
+    }
+    __syncthreads();
+    const uint64_t dbad = s_dbad, ebad = s_ebad;
+    int32_t st = top;
+    uint64_t bad_seg = kNoSeg;
+    if (dbad != kNoSeg) {
+        st = decoded_verdict(w.d_status[dbad], w.d_out_lens[dbad], w.d_out_caps[dbad]);
+        bad_seg = seg_d(dbad);
+    } else if (ebad != kNoSeg) {
+        st = w.status[ebad];
+        bad_seg = seg_c(ebad);
+    }
+    if (st == 0) return false;
+    if (threadIdx.x == 0) {
+        *o.status = st;
+        *o.out_len = 0;
+        if (o.bad_segment) *o.bad_segment = bad_seg;
+        w.ctl[0] = 0;
+        w.ctl[1] = 0;
+    }
+    return true;
+}
+// The verdict after the pieces, by one thread: the container ends at `end`, the spliced bytes at `spliced`
+__device__ __forceinline__ void seal_fits(const CodedWs &w, const WriteOut &o, uint64_t out_cap, uint64_t end,
+                                          uint64_t spliced)
+{
+    const bool fits = end <= out_cap;
+    *o.status = fits ? 0 : HC_ERR_CAPACITY;
+    *o.out_len = end;
+    if (o.bad_segment) *o.bad_segment = kNoSeg;
+    w.ctl[0] = fits ? 1 : 0;
+    w.ctl[1] = spliced;
+}
+
+struct UpdWs {
+    PatchRec *recs;
+    uint64_t *pk_src, *pk_len, *pk_dst;      // per patch
+    uint64_t *d_cov;                         // per decoded entry: its covered entry
+    uint64_t *cov_seg, *old_off, *old_len;   // per covered entry: its segment and that segment's old place
+    CodedWs co;                              // the covered entries are the coded ones; 4 ctl words
+    uint64_t total;
 };
 UpdWs carve_upd(void *work, uint64_t P, uint64_t D, uint64_t C, bool check, uint64_t stage_bytes, uint64_t slot_bytes,
                 uint64_t awork_bytes)
 {
     UpdWs w;
-    uint8_t *p = static_cast<uint8_t *>(work);
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p ? p + o : nullptr;  // null: sizing only
-        o += align16(bytes);
-        return q;
-    };
-    auto take64 = [&](uint64_t n) { return reinterpret_cast<uint64_t *>(take(8 * n)); };
-    w.recs = reinterpret_cast<PatchRec *>(take(sizeof(PatchRec) * P));
-    w.pk_src = take64(P);
-    w.pk_len = take64(P);
-    w.pk_dst = take64(P);
-    w.d_cov = take64(D);
-    w.d_in_offs = take64(D);
-    w.d_in_lens = take64(D);
-    w.d_out_offs = take64(D);
-    w.d_out_caps = take64(D);
-    w.d_out_lens = take64(D);
-    w.d_status = reinterpret_cast<int32_t *>(take(4 * D));
-    w.d_crc = reinterpret_cast<uint32_t *>(take(check ? 4 * D : 0));
-    w.cov_seg = take64(C);
-    w.old_off = take64(C);
-    w.old_len = take64(C);
-    w.in_offs = take64(C);
-    w.in_lens = take64(C);
-    w.widths = take64(C);
-    w.slot_offs = take64(C);
-    w.slot_caps = take64(C);
-    w.enc_lens = take64(C);
-    w.status = reinterpret_cast<int32_t *>(take(4 * C));
-    w.crc = reinterpret_cast<uint32_t *>(take(check ? 4 * C : 0));
-    w.pc_src = take64(2 * C + 1);
-    w.pc_dst = take64(2 * C + 1);
-    w.pc_len = take64(2 * C + 1);
-    w.ctl = take64(4);
-    w.stage = take(stage_bytes);
-    w.slots = take(slot_bytes);
-    w.awork = take(awork_bytes);
-    w.awork_bytes = awork_bytes;
-    w.total = o;
+    Carver cv(work);
+    w.recs = cv.arr<PatchRec>(P);
+    w.pk_src = cv.take64(P);
+    w.pk_len = cv.take64(P);
+    w.pk_dst = cv.take64(P);
+    w.d_cov = cv.take64(D);
+    w.cov_seg = cv.take64(C);
+    w.old_off = cv.take64(C);
+    w.old_len = cv.take64(C);
+    w.co = carve_coded(cv, C, D, check, 4, stage_bytes, slot_bytes, awork_bytes);
+    w.total = cv.total();
     return w;
 }
 static_assert(sizeof(PatchRec) == 64, "the work bound of hcodec.h counts this");
@@ -1125,13 +1305,12 @@ struct UpdCall {
     const uint8_t *in;
     uint8_t *out;
     uint64_t in_len, out_cap;
-    uint64_t magic, flags, raw_len, seg_bytes, width, n;  // the header words, the caller's host copy
+    HeaderWords h;  // the caller's host copy
     uint64_t full, last, slot_full, cap_full, cap_last;
     uint64_t P, D, C;
     uint32_t check;
     UpdWs w;
-    uint64_t *out_len, *bad_segment;
-    int32_t *status_out;
+    WriteOut o;
 };
 
 struct PatchChunk {
@@ -1170,130 +1349,56 @@ __global__ __launch_bounds__(256) void seg_uplan_kernel(UpdCall a)
         else hi = mid;
     }
     const uint64_t k = a.w.recs[lo].k0 + (c - a.w.recs[lo].e0);
-    const bool tail = k == a.n - 1;
+    const bool tail = k == a.h.n - 1;
     a.w.cov_seg[c] = k;
     a.w.old_off[c] = 0;
     a.w.old_len[c] = 0;
-    a.w.in_offs[c] = c * a.full;
-    a.w.in_lens[c] = tail ? a.last : a.full;
-    a.w.widths[c] = a.width;
-    a.w.slot_offs[c] = c * a.slot_full;
-    a.w.slot_caps[c] = tail ? a.cap_last : a.cap_full;
-    a.w.enc_lens[c] = 0;
-    a.w.status[c] = HC_ERR_DEVICE;  // overwritten by the encode launch
+    plan_coded(a.w.co, c, c * a.full, tail ? a.last : a.full, a.h.width, c * a.slot_full, tail ? a.cap_last : a.cap_full);
 }
 
-// seg_open_kernel's checks and scan for a range write: the old place of every covered segment
-// (found in cov_seg, which ascends, by search), then the decoder's arrays from those. On failure
-// every decoder input is empty: nothing of the container is read. (The encoders still code what
-// the staging region holds, into their slots; the seal's verdict keeps it from out.)
+// scan_index for a range write: the old place of every covered segment (found in cov_seg, which
+// ascends, by search), then the decoder's arrays from those. On failure every decoder input is
+// empty: nothing of the container is read. (The encoders still code what the staging region
+// holds, into their slots; the seal's verdict keeps it from out.)
 __global__ __launch_bounds__(kScan) void seg_uopen_kernel(UpdCall a)
 {
-    __shared__ uint64_t part[kScan / 64];
-    __shared__ uint32_t s_err;
     const uint32_t tid = threadIdx.x;
-    if (tid == 0) s_err = 0;
-    __syncthreads();
-    bool err = false;
-    const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in);
-    if (tid < 6) {
-        const uint64_t want = tid == 0 ? a.magic : tid == 1 ? a.flags : tid == 2 ? a.raw_len
-                              : tid == 3 ? a.seg_bytes : tid == 4 ? a.width : a.n;
-        if (i64[tid] != want) err = true;
-    }
-    uint64_t carry = align16(index_end(a.n, a.check != 0));
-    for (uint64_t base = 0; base < a.n; base += kScan) {
-        const uint64_t k = base + tid;
-        const bool in = k < a.n;
-        const uint64_t len = in ? i64[6 + k] : 0;
-        const bool big = len > a.in_len;
-        uint64_t total;
-        const uint64_t off = sat_add(carry, block_scan(in && !big ? align16(len) : 0, part, total));
-        if (in) {
-            if (big || off > a.in_len || len > a.in_len - off) err = true;
-            else if (k == a.n - 1 && off + len != a.in_len) err = true;  // truncated, or trailing bytes
-            uint64_t lo = 0, hi = a.C;  // the first entry whose segment is >= k
-            while (lo < hi) {
-                const uint64_t mid = lo + (hi - lo) / 2;
-                if (a.w.cov_seg[mid] < k) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < a.C && a.w.cov_seg[lo] == k) {
-                a.w.old_off[lo] = off;
-                a.w.old_len[lo] = len;
-            }
+    const UpdWs &w = a.w;
+    const bool bad = scan_index(a.in, a.h, a.in_len, a.check != 0, [&](uint64_t k, uint64_t off, uint64_t len) {
+        uint64_t lo = 0, hi = a.C;  // the first entry whose segment is >= k
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (w.cov_seg[mid] < k) lo = mid + 1;
+            else hi = mid;
         }
-        carry = sat_add(carry, total);
-    }
-    if (err) s_err = 1;
-    __syncthreads();
-    const bool bad = s_err != 0;
-    if (tid == 0) a.w.ctl[2] = bad ? (uint64_t)HC_ERR_SEG_HEADER : 0;
+        if (lo < a.C && w.cov_seg[lo] == k) {
+            w.old_off[lo] = off;
+            w.old_len[lo] = len;
+        }
+    });
+    if (tid == 0) w.co.ctl[2] = bad ? (uint64_t)HC_ERR_SEG_HEADER : 0;
     for (uint64_t d = tid; d < a.D; d += kScan) {
-        const uint64_t c = a.w.d_cov[d];
-        a.w.d_in_offs[d] = bad ? 0 : a.w.old_off[c];
-        a.w.d_in_lens[d] = bad ? 0 : a.w.old_len[c];
-        a.w.d_out_offs[d] = c * a.full;
-        a.w.d_out_caps[d] = a.w.cov_seg[c] == a.n - 1 ? a.last : a.full;
-        a.w.d_out_lens[d] = 0;
-        a.w.d_status[d] = HC_ERR_DEVICE;  // overwritten by the decode launch
+        const uint64_t c = w.d_cov[d];
+        plan_decoded(w.co, d, bad, w.old_off[c], w.old_len[c], c * a.full, w.cov_seg[c] == a.h.n - 1 ? a.last : a.full);
     }
 }
 
-// The verdict (the lowest failing decoded entry by seg_close_kernel's mapping, then the capacity)
-// and the pieces. Piece p starts at the sum of align16(length) of the pieces before it.
+// The verdict (seal_failed, then the capacity) and the pieces. Piece p starts at the sum of
+// align16(length) of the pieces before it.
 __global__ __launch_bounds__(kScan) void seg_useal_kernel(UpdCall a)
 {
     __shared__ uint64_t part[kScan / 64];
-    __shared__ unsigned long long s_bad, s_ebad, s_end;
+    __shared__ unsigned long long s_end;
     const uint32_t tid = threadIdx.x;
-    const UpdWs &w = a.w;
-    if (tid == 0) {
-        s_bad = kNoSeg;
-        s_ebad = kNoSeg;
-        s_end = 0;
-    }
-    __syncthreads();
-    const int32_t top = (int32_t)w.ctl[2];
-    const uint32_t *want_crc = reinterpret_cast<const uint32_t *>(a.in + 48 + 8 * a.n);
-    if (top == 0) {
-        uint64_t bad = kNoSeg;
-        for (uint64_t d = tid; d < a.D && bad == kNoSeg; d += kScan)
-            if (w.d_status[d] != 0 || w.d_out_lens[d] != w.d_out_caps[d] ||
-                (a.check && w.d_crc[d] != want_crc[w.cov_seg[w.d_cov[d]]]))
-                bad = d;
-        if (bad != kNoSeg) atomicMin(&s_bad, (unsigned long long)bad);
-        bad = kNoSeg;  // (an encoder never fails in a bound-sized slot; if one does, the call must not succeed)
-        for (uint64_t c = tid; c < a.C && bad == kNoSeg; c += kScan)
-            if (w.status[c] != 0) bad = c;
-        if (bad != kNoSeg) atomicMin(&s_ebad, (unsigned long long)bad);
-    }
-    __syncthreads();
-    const uint64_t dbad = s_bad, ebad = s_ebad;
-    int32_t st = top;
-    uint64_t bad_seg = kNoSeg;
-    if (top == 0 && dbad != kNoSeg) {
-        st = w.d_status[dbad];
-        if (st == 0 && w.d_out_lens[dbad] == w.d_out_caps[dbad]) st = HC_ERR_SEG_CHECK;
-        else if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
-        bad_seg = w.cov_seg[w.d_cov[dbad]];
-    } else if (top == 0 && ebad != kNoSeg) {
-        st = w.status[ebad];
-        bad_seg = w.cov_seg[ebad];
-    }
-    if (st != 0) {
-        if (tid == 0) {
-            *a.status_out = st;
-            *a.out_len = 0;
-            if (a.bad_segment) *a.bad_segment = bad_seg;
-            w.ctl[0] = 0;
-            w.ctl[1] = 0;
-        }
+    const UpdWs &u = a.w;
+    const CodedWs &w = u.co;
+    const uint32_t *want_crc = a.check ? reinterpret_cast<const uint32_t *>(a.in + 48 + 8 * a.h.n) : nullptr;
+    if (seal_failed(w, a.D, a.C, want_crc, a.o, [&](uint64_t d) { return u.cov_seg[u.d_cov[d]]; },
+                    [&](uint64_t c) { return u.cov_seg[c]; }))
         return;
-    }
     // the index tiles the old container exactly (uopen), so no sum below can wrap
     const uint64_t pieces = 2 * a.C + 1;
-    const bool tail_covered = a.C && w.cov_seg[a.C - 1] == a.n - 1;
+    const bool tail_covered = a.C && u.cov_seg[a.C - 1] == a.h.n - 1;
     uint64_t carry = 0;
     for (uint64_t base = 0; base < pieces; base += kScan) {
         const uint64_t p = base + tid, j = p >> 1;
@@ -1303,8 +1408,8 @@ __global__ __launch_bounds__(kScan) void seg_useal_kernel(UpdCall a)
             src = w.slot_offs[j];
             len = w.enc_lens[j];
         } else if (in) {
-            const uint64_t be = j == a.C ? a.in_len : w.old_off[j];
-            src = j == 0 ? 0 : align16(w.old_off[j - 1] + w.old_len[j - 1]);
+            const uint64_t be = j == a.C ? a.in_len : u.old_off[j];
+            src = j == 0 ? 0 : align16(u.old_off[j - 1] + u.old_len[j - 1]);
             if (src > be) src = be;  // after the container's last segment
             len = be - src;
         }
@@ -1320,14 +1425,7 @@ __global__ __launch_bounds__(kScan) void seg_useal_kernel(UpdCall a)
         carry += total;
     }
     __syncthreads();
-    if (tid != 0) return;
-    const uint64_t end = s_end;
-    const bool fits = end <= a.out_cap;
-    *a.status_out = fits ? 0 : HC_ERR_CAPACITY;
-    *a.out_len = end;
-    if (a.bad_segment) *a.bad_segment = kNoSeg;
-    w.ctl[0] = fits ? 1 : 0;
-    w.ctl[1] = end;
+    if (tid == 0) seal_fits(w, a.o, a.out_cap, s_end, s_end);
 }
 
 // The pieces to their places. Output chunk g (16 bytes at 16 g) belongs to the last piece whose
@@ -1337,17 +1435,24 @@ __global__ __launch_bounds__(kScan) void seg_useal_kernel(UpdCall a)
 // hundreds of megabytes is as many workgroups' work as its bytes call for. Sources and
 // destinations are 16-byte aligned. A piece's last chunk, when it is short, goes out byte by byte
 // with its padding zeroed, except at the container's end, where nothing follows the last byte.
-__global__ __launch_bounds__(256) void seg_usplice_kernel(UpdCall a)
+struct SpliceCall {
+    const uint8_t *in;     // the even pieces' source: the old container
+    const uint8_t *slots;  // the odd pieces' source
+    uint8_t *out;
+    const uint64_t *pc_src, *pc_dst, *pc_len;
+    const uint64_t *ctl;  // [0] 1: sealed; [1] the spliced bytes' end
+    uint64_t pieces;
+};
+__global__ __launch_bounds__(256) void seg_splice_kernel(SpliceCall a)
 {
     __shared__ uint64_t s_p[2];
-    const UpdWs &w = a.w;
-    if (w.ctl[0] == 0) return;  // not sealed: nothing is copied
-    const uint64_t end = w.ctl[1], chunks = (end + 15) / 16, pieces = 2 * a.C + 1;
+    if (a.ctl[0] == 0) return;  // not sealed: nothing is copied
+    const uint64_t end = a.ctl[1], chunks = (end + 15) / 16, pieces = a.pieces;
     constexpr uint64_t kTile = 256ull * kSpliceChunks;
     auto find = [&](uint64_t x, uint64_t lo, uint64_t hi) {  // pc_dst[lo] <= x; hi: one past the candidates
         while (hi - lo > 1) {
             const uint64_t mid = lo + (hi - lo) / 2;
-            if (w.pc_dst[mid] <= x) lo = mid;
+            if (a.pc_dst[mid] <= x) lo = mid;
             else hi = mid;
         }
         return lo;
@@ -1369,10 +1474,10 @@ __global__ __launch_bounds__(256) void seg_usplice_kernel(UpdCall a)
             src[i] = nullptr;
             last_piece[i] = false;
             if (g > g1) continue;
-            const uint64_t p = find(16 * g, p_lo, p_hi), off = 16 * g - w.pc_dst[p], len = w.pc_len[p];
+            const uint64_t p = find(16 * g, p_lo, p_hi), off = 16 * g - a.pc_dst[p], len = a.pc_len[p];
             if (off >= len) continue;  // (never: a piece's chunks end with its last byte's)
             rest[i] = len - off;
-            src[i] = reinterpret_cast<const u32x4 *>(((p & 1) ? w.slots : a.in) + w.pc_src[p] + off);
+            src[i] = reinterpret_cast<const u32x4 *>(((p & 1) ? a.slots : a.in) + a.pc_src[p] + off);
             last_piece[i] = 16 * g + rest[i] == end;
         }
         u32x4 v[kSpliceChunks];
@@ -1399,43 +1504,98 @@ __global__ __launch_bounds__(256) void seg_usplice_kernel(UpdCall a)
 __global__ __launch_bounds__(256) void seg_uindex_kernel(UpdCall a)
 {
     const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (c >= a.C || a.w.ctl[0] == 0) return;
+    if (c >= a.C || a.w.co.ctl[0] == 0) return;
     const uint64_t k = a.w.cov_seg[c];
-    reinterpret_cast<uint64_t *>(a.out)[6 + k] = a.w.enc_lens[c];
-    if (a.check) reinterpret_cast<uint32_t *>(a.out)[12 + 2 * a.n + k] = a.w.crc[c];
+    reinterpret_cast<uint64_t *>(a.out)[6 + k] = a.w.co.enc_lens[c];
+    if (a.check) reinterpret_cast<uint32_t *>(a.out)[12 + 2 * a.h.n + k] = a.w.co.crc[c];
+}
+
+// What both write calls size their coded entries by: the slots of a full cut and of the new
+// container's last one, and the adaptive coders' workspace.
+struct CodedSizes {
+    uint64_t cap_full, cap_last, slot_full, slot_bytes, awork_bytes;
+    bool adapt, check;
+};
+CodedSizes coded_sizes(const hc_seg_info_t &info, uint64_t full, uint64_t last)
+{
+    CodedSizes s;
+    s.adapt = (info.flags & HC_FLAG_ADAPT) != 0;
+    s.check = checked(info.flags);
+    s.cap_full = hc_compress_bound(full, s.adapt);
+    s.cap_last = hc_compress_bound(last, s.adapt);
+    s.slot_full = align16(s.cap_full);
+    s.slot_bytes = s.awork_bytes = 0;
+    return s;
+}
+// C entries of coded_raw bytes in all are coded after D entries of dec_raw bytes, out of dec_in
+// bytes of streams, are decoded (more than kMaxSegs entries: the caller refuses the call)
+uint64_t coded_awork(bool adapt, uint64_t C, uint64_t coded_raw, uint64_t D, uint64_t dec_in, uint64_t dec_raw)
+{
+    if (!adapt || C > kMaxSegs) return 0;
+    const uint64_t e = C ? hc::adapt_encode_work_bound(coded_raw, (uint32_t)C) : 0;
+    const uint64_t d = D ? hc::adapt_decode_work_bound(dec_in, dec_raw, (uint32_t)D) : 0;
+    return e > d ? e : d;  // the decode launch is over before the encode launch starts
+}
+
+// The coder launches of a write call, in the two halves that the append plans between. First the
+// D decoded entries from the old container into the staging region and, in a checked container,
+// the CRC-32 of those that decoded cleanly to their cut's length.
+int decode_to_stage(const uint8_t *in, const CodedWs &w, uint64_t D, const CodedSizes &s, hipStream_t st)
+{
+    if (!D) return HC_OK;
+    Batch b{in, w.d_in_offs, w.d_in_lens, (uint32_t)D, w.stage, w.d_out_offs, w.d_out_caps, w.d_out_lens, w.d_status, 0};
+    if (s.adapt) HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
+    else HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
+    if (s.check)
+        HC_CK(hc::launch_crc32(w.stage, w.d_out_offs, w.d_out_caps, D, w.d_crc, hc::CrcGate{w.d_status, w.d_out_lens}, st));
+    return HC_OK;
+}
+// Then n_pack ranges of new bytes from `src` over the staging region, at any byte alignment (an
+// empty range costs nothing), in a checked container the CRC-32 of the C coded cuts, and the
+// encode launch into the slots.
+int code_from_stage(const uint8_t *src, const uint64_t *pk_src, const uint64_t *pk_len, const uint64_t *pk_dst,
+                    uint32_t n_pack, const CodedWs &w, uint64_t C, const CodedSizes &s, uint32_t flags, hipStream_t st)
+{
+    if (!C) return HC_OK;
+    HC_CK(hc::launch_pack(src, pk_src, pk_len, n_pack, w.stage, pk_dst, st));
+    Batch b{w.stage, w.in_offs, w.in_lens, (uint32_t)C, w.slots, w.slot_offs, w.slot_caps, w.enc_lens, w.status,
+            flags & HC_FLAG_DIFF};
+    if (s.check) HC_CK(hc::launch_crc32(w.stage, w.in_offs, w.in_lens, C, w.crc, hc::CrcGate{nullptr, nullptr}, st));
+    if (s.adapt) HC_CK(hc::adapt_encode_batch(b, w.widths, w.awork, w.awork_bytes, st));
+    else HC_CK(hc::launch_encode(b, (flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
+    return HC_OK;
+}
+// The splice over the seal's pieces; the grid by the longest result there can be (the rest by stride)
+void launch_splice(const uint8_t *in, uint8_t *out, const CodedWs &w, uint64_t C, uint64_t longest, hipStream_t st)
+{
+    const uint64_t tiles = longest / (4096ull * kSpliceChunks) + 1;
+    seg_splice_kernel<<<(uint32_t)(tiles < 4096 ? tiles : 4096), 256, 0, st>>>(
+        SpliceCall{in, w.slots, out, w.pc_src, w.pc_dst, w.pc_len, w.ctl, 2 * C + 1});
 }
 
 // the sizes of a range write whose info passed info_ok and whose patches passed patches_ok
 struct UpdSizes {
     Cuts c;
     UpdPlan u;
-    uint64_t cap_full, cap_last, slot_full, stage_bytes, slot_bytes, awork_bytes;
-    bool adapt, check;
+    CodedSizes co;
+    uint64_t stage_bytes;
 };
 UpdSizes upd_sizes(const hc_seg_info_t &info, uint64_t in_len, const hc_seg_patch_t *patches, uint32_t n_patches,
                    PatchRec *recs)
 {
     UpdSizes s;
     (void)info_ok(info, in_len, s.c);
-    s.adapt = (info.flags & HC_FLAG_ADAPT) != 0;
-    s.check = checked(info.flags);
-    s.cap_full = hc_compress_bound(s.c.full, s.adapt);
-    s.cap_last = hc_compress_bound(s.c.last, s.adapt);
-    s.slot_full = align16(s.cap_full);
-    s.u = hc_seg_index::update_plan(s.c, info.raw_len, patches, n_patches, s.slot_full, align16(s.cap_last), recs);
+    s.co = coded_sizes(info, s.c.full, s.c.last);
+    s.u = hc_seg_index::update_plan(s.c, info.raw_len, patches, n_patches, s.co.slot_full, align16(s.co.cap_last), recs);
     s.stage_bytes = align16(s.u.cov_raw);
-    s.slot_bytes = s.u.cov_bound;
-    s.awork_bytes = 0;
-    if (s.adapt && s.u.covered <= kMaxSegs) {
-        const uint64_t e = s.u.covered ? hc::adapt_encode_work_bound(s.u.cov_raw, (uint32_t)s.u.covered) : 0;
-        const uint64_t d = s.u.decoded ? hc::adapt_decode_work_bound(in_len, s.u.dec_raw, (uint32_t)s.u.decoded) : 0;
-        s.awork_bytes = e > d ? e : d;  // the decode launch is over before the encode launch starts
-    }
+    s.co.slot_bytes = s.u.cov_bound;
+    s.co.awork_bytes = coded_awork(s.co.adapt, s.u.covered, s.u.cov_raw, s.u.decoded, in_len, s.u.dec_raw);
     return s;
 }
 UpdWs upd_ws(void *work, const UpdSizes &s, uint32_t n_patches)
 {
-    return carve_upd(work, n_patches, s.u.decoded, s.u.covered, s.check, s.stage_bytes, s.slot_bytes, s.awork_bytes);
+    return carve_upd(work, n_patches, s.u.decoded, s.u.covered, s.co.check, s.stage_bytes, s.co.slot_bytes,
+                     s.co.awork_bytes);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1445,17 +1605,18 @@ UpdWs upd_ws(void *work, const UpdSizes &s, uint32_t n_patches)
 // only segment that is ever decoded) and the added bytes. Coded entry c keeps its raw bytes at
 // c full of a staging region and its new stream in a bound-sized slot, as in the range write.
 //
-//   aopen    one workgroup: header against the caller's copy, scan of the whole index, the kept
-//            block (segment 0's first byte to segment K - 1's last), the decoder's one entry
-//   <decode launch of old segment n - 1 to staging offset 0; checked containers: its CRC-32>
+//   aopen    one workgroup: header against the caller's copy, scan of the whole index (scan_index),
+//            the kept block (segment 0's first byte to segment K - 1's last), the decoder's one entry
+//   <decode_to_stage: decode launch of old segment n - 1 to staging offset 0; checked containers:
+//    its CRC-32>
 //   aplan    coded entry c: its staging range, its slot, its own part of the added bytes as one
 //            pack range (so a large append packs on as many workgroups as it codes segments)
-//   <pack launch: the added bytes behind the open tail, at any byte alignment>
-//   <checked containers: CRC-32 of the coded cuts; encode launch into the slots>
-//   aseal    one workgroup: the verdict, the new segments' places, and the copy pieces in
-//            seg_usplice_kernel's layout (2 C + 1 of them: the kept block at 0, coded entry c's
-//            slot at 2 c + 1, nothing at the other even places)
-//   usplice  the range write's splice kernel moves the pieces, 16 bytes per lane; gated
+//   <code_from_stage: pack launch, the added bytes behind the open tail, at any byte alignment;
+//    checked containers: CRC-32 of the coded cuts; encode launch into the slots>
+//   aseal    one workgroup: the verdict (seal_failed, seal_fits), the new segments' places, and the
+//            copy pieces in the range write's layout (2 C + 1 of them: the kept block at 0, coded
+//            entry c's slot at 2 c + 1, nothing at the other even places)
+//   splice   the range write's splice kernel moves the pieces, 16 bytes per lane; gated
 //   aindex   the new header words, enc_len[0 .. n'), crc[0 .. n') (kept entries from the old index
 //            at its old place), the zero padding up to the first segment; gated
 //
@@ -1467,58 +1628,21 @@ UpdWs upd_ws(void *work, const UpdSizes &s, uint32_t n_patches)
 using hc_seg_index::AppPlan;
 
 struct AppWs {
-    uint64_t *in_offs, *in_lens, *widths, *slot_offs, *slot_caps, *enc_lens, *pk_src, *pk_len, *pk_dst;  // per coded entry
-    int32_t *status;
-    uint32_t *crc;  // checked containers
-    uint64_t *pc_src, *pc_dst, *pc_len;  // per piece
-    uint64_t *d_in_off, *d_in_len, *d_out_off, *d_out_cap, *d_out_len;  // the decoder's one entry
-    int32_t *d_status;
-    uint32_t *d_crc;  // checked containers
-    // [0] 1: sealed, the splice may copy; [1] the spliced bytes' end; [2] aopen's verdict; [3], [4] the
-    // kept block's first byte in `in` and its length
-    uint64_t *ctl;
-    uint8_t *stage, *slots;
-    void *awork;
-    uint64_t awork_bytes, total;
+    // the one decoded entry is carved whether the call decodes or not; 8 ctl words: [3], [4] the kept
+    // block's first byte in `in` and its length
+    CodedWs co;
+    uint64_t *pk_src, *pk_len, *pk_dst;  // per coded entry: its part of the added bytes
+    uint64_t total;
 };
 AppWs carve_app(void *work, uint64_t C, bool check, uint64_t stage_bytes, uint64_t slot_bytes, uint64_t awork_bytes)
 {
     AppWs w;
-    uint8_t *p = static_cast<uint8_t *>(work);
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) {
-        uint8_t *q = p ? p + o : nullptr;  // null: sizing only
-        o += align16(bytes);
-        return q;
-    };
-    auto take64 = [&](uint64_t n) { return reinterpret_cast<uint64_t *>(take(8 * n)); };
-    w.in_offs = take64(C);
-    w.in_lens = take64(C);
-    w.widths = take64(C);
-    w.slot_offs = take64(C);
-    w.slot_caps = take64(C);
-    w.enc_lens = take64(C);
-    w.pk_src = take64(C);
-    w.pk_len = take64(C);
-    w.pk_dst = take64(C);
-    w.status = reinterpret_cast<int32_t *>(take(4 * C));
-    w.crc = reinterpret_cast<uint32_t *>(take(check ? 4 * C : 0));
-    w.pc_src = take64(2 * C + 1);
-    w.pc_dst = take64(2 * C + 1);
-    w.pc_len = take64(2 * C + 1);
-    w.d_in_off = take64(1);
-    w.d_in_len = take64(1);
-    w.d_out_off = take64(1);
-    w.d_out_cap = take64(1);
-    w.d_out_len = take64(1);
-    w.d_status = reinterpret_cast<int32_t *>(take(4));
-    w.d_crc = reinterpret_cast<uint32_t *>(take(check ? 4 : 0));
-    w.ctl = take64(8);
-    w.stage = take(stage_bytes);
-    w.slots = take(slot_bytes);
-    w.awork = take(awork_bytes);
-    w.awork_bytes = awork_bytes;
-    w.total = o;
+    Carver cv(work);
+    w.pk_src = cv.take64(C);
+    w.pk_len = cv.take64(C);
+    w.pk_dst = cv.take64(C);
+    w.co = carve_coded(cv, C, 1, check, 8, stage_bytes, slot_bytes, awork_bytes);
+    w.total = cv.total();
     return w;
 }
 
@@ -1527,78 +1651,40 @@ struct AppCall {
     const uint8_t *in;
     uint8_t *out;
     uint64_t in_len, out_cap, skip;
-    uint64_t magic, flags, raw_len, seg_bytes, width, n;  // the old header words, the caller's host copy
-    uint64_t full, last;                                  // the old cuts
+    HeaderWords h;         // the old header, the caller's host copy
+    uint64_t full, last;   // the old cuts
     uint64_t new_raw, new_n, new_last;                    // the new header words and the new last cut
     uint64_t K, C, D, tail, add_len;
     uint64_t slot_full, cap_full, cap_last;
     uint32_t check, gather;
     AppWs w;
-    uint64_t *out_len, *bad_segment;
-    int32_t *status_out;
+    WriteOut o;
 };
 
-// seg_uopen_kernel's checks and scan for an append: where the kept block ends and where old segment
-// n - 1 lies. On failure the decoder's input is empty: nothing of the container is read.
+// scan_index for an append: where the kept block ends and where old segment n - 1 lies. On failure
+// the decoder's input is empty: nothing of the container is read.
 __global__ __launch_bounds__(kScan) void seg_aopen_kernel(AppCall a)
 {
-    __shared__ uint64_t part[kScan / 64];
-    __shared__ uint32_t s_err;
     __shared__ uint64_t s_kept_end, s_last_off, s_last_len;
     const uint32_t tid = threadIdx.x;
-    const uint64_t first = align16(index_end(a.n, a.check != 0));
+    const uint64_t first = align16(index_end(a.h.n, a.check != 0));
     if (tid == 0) {
-        s_err = 0;
         s_kept_end = first;
         s_last_off = s_last_len = 0;
     }
-    __syncthreads();
-    bool err = false;
-    const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in);
-    if (tid < 6) {
-        const uint64_t want = tid == 0 ? a.magic : tid == 1 ? a.flags : tid == 2 ? a.raw_len
-                              : tid == 3 ? a.seg_bytes : tid == 4 ? a.width : a.n;
-        if (i64[tid] != want) err = true;
-    }
-    uint64_t carry = first;
-    for (uint64_t base = 0; base < a.n; base += kScan) {
-        const uint64_t k = base + tid;
-        const bool in = k < a.n;
-        const uint64_t len = in ? i64[6 + k] : 0;
-        const bool big = len > a.in_len;
-        uint64_t total;
-        const uint64_t off = sat_add(carry, block_scan(in && !big ? align16(len) : 0, part, total));
-        if (in) {
-            if (big || off > a.in_len || len > a.in_len - off) {
-                err = true;
-            } else if (k == a.n - 1 && off + len != a.in_len) {
-                err = true;  // truncated, or trailing bytes
-            } else {
-                if (k + 1 == a.K) s_kept_end = off + len;
-                if (k == a.n - 1) {
-                    s_last_off = off;
-                    s_last_len = len;
-                }
-            }
+    const bool bad = scan_index(a.in, a.h, a.in_len, a.check != 0, [&](uint64_t k, uint64_t off, uint64_t len) {
+        if (k + 1 == a.K) s_kept_end = off + len;
+        if (k == a.h.n - 1) {
+            s_last_off = off;
+            s_last_len = len;
         }
-        carry = sat_add(carry, total);
-    }
-    if (err) s_err = 1;
-    __syncthreads();
+    });
     if (tid != 0) return;
-    const bool bad = s_err != 0;
-    const AppWs &w = a.w;
+    const CodedWs &w = a.w.co;
     w.ctl[2] = bad ? (uint64_t)HC_ERR_SEG_HEADER : 0;
     w.ctl[3] = first;
     w.ctl[4] = bad ? 0 : s_kept_end - first;  // (K == 0: nothing is kept)
-    if (a.D) {
-        w.d_in_off[0] = bad ? 0 : s_last_off - a.skip;
-        w.d_in_len[0] = bad ? 0 : s_last_len;
-        w.d_out_off[0] = 0;
-        w.d_out_cap[0] = a.last;
-        w.d_out_len[0] = 0;
-        w.d_status[0] = HC_ERR_DEVICE;  // overwritten by the decode launch
-    }
+    if (a.D) plan_decoded(w, 0, bad, s_last_off - a.skip, s_last_len, 0, a.last);
 }
 
 // coded entry c: its staging range, its slot, and the added bytes that fall into its cut: the
@@ -1610,17 +1696,11 @@ __global__ __launch_bounds__(256) void seg_aplan_kernel(AppCall a)
     const AppWs &w = a.w;
     const bool tail = c == a.C - 1;
     const uint64_t b = c * a.full, e = b + (tail ? a.new_last : a.full);
-    w.in_offs[c] = b;
-    w.in_lens[c] = e - b;
-    w.widths[c] = a.width;
-    w.slot_offs[c] = c * a.slot_full;
-    w.slot_caps[c] = tail ? a.cap_last : a.cap_full;
-    w.enc_lens[c] = 0;
-    w.status[c] = HC_ERR_DEVICE;  // overwritten by the encode launch
     const uint64_t lo = b > a.tail ? b : a.tail;  // (e <= tail + add_len: the cuts end with the added bytes)
     w.pk_src[c] = lo < e ? lo - a.tail : 0;
     w.pk_len[c] = lo < e ? e - lo : 0;
     w.pk_dst[c] = lo < e ? lo : 0;
+    plan_coded(w.co, c, b, e - b, a.h.width, c * a.slot_full, tail ? a.cap_last : a.cap_full);
 }
 
 // The verdict (the decoded segment by seg_close_kernel's mapping, then the capacity), the new
@@ -1630,48 +1710,16 @@ __global__ __launch_bounds__(256) void seg_aplan_kernel(AppCall a)
 __global__ __launch_bounds__(kScan) void seg_aseal_kernel(AppCall a)
 {
     __shared__ uint64_t part[kScan / 64];
-    __shared__ unsigned long long s_ebad, s_end;
+    __shared__ unsigned long long s_end;
     const uint32_t tid = threadIdx.x;
-    const AppWs &w = a.w;
-    const int32_t top = (int32_t)w.ctl[2];
+    const CodedWs &w = a.w.co;
     const uint64_t kept_len = w.ctl[4];
     const uint64_t first = align16(index_end(a.new_n, a.check != 0)), base0 = first + align16(kept_len);
-    if (tid == 0) {
-        s_ebad = kNoSeg;
-        s_end = first + kept_len;  // no coded entry: nothing is added, the kept block is the old container's rest
-    }
-    __syncthreads();
-    if (top == 0) {  // (an encoder never fails in a bound-sized slot; if one does, the call must not succeed)
-        uint64_t bad = kNoSeg;
-        for (uint64_t c = tid; c < a.C && bad == kNoSeg; c += kScan)
-            if (w.status[c] != 0) bad = c;
-        if (bad != kNoSeg) atomicMin(&s_ebad, (unsigned long long)bad);
-    }
-    __syncthreads();
-    const uint64_t ebad = s_ebad;
-    int32_t st = top;
-    uint64_t bad_seg = kNoSeg;
-    const uint32_t *want_crc = reinterpret_cast<const uint32_t *>(a.in + 48 + 8 * a.n);
-    if (top == 0 && a.D &&
-        (w.d_status[0] != 0 || w.d_out_len[0] != w.d_out_cap[0] || (a.check && w.d_crc[0] != want_crc[a.n - 1]))) {
-        st = w.d_status[0];
-        if (st == 0 && w.d_out_len[0] == w.d_out_cap[0]) st = HC_ERR_SEG_CHECK;
-        else if (st == 0 || st == HC_ERR_CAPACITY) st = HC_ERR_SEG_SIZE;
-        bad_seg = a.n - 1;
-    } else if (top == 0 && ebad != kNoSeg) {
-        st = w.status[ebad];
-        bad_seg = a.K + ebad;
-    }
-    if (st != 0) {
-        if (tid == 0) {
-            *a.status_out = st;
-            *a.out_len = 0;
-            if (a.bad_segment) *a.bad_segment = bad_seg;
-            w.ctl[0] = 0;
-            w.ctl[1] = 0;
-        }
+    // no coded entry: nothing is added, the kept block is the old container's rest
+    if (tid == 0) s_end = first + kept_len;
+    const uint32_t *want_crc = a.check ? reinterpret_cast<const uint32_t *>(a.in + 48 + 8 * a.h.n) : nullptr;
+    if (seal_failed(w, a.D, a.C, want_crc, a.o, [&](uint64_t) { return a.h.n - 1; }, [&](uint64_t c) { return a.K + c; }))
         return;
-    }
     // the index tiles the old container exactly (aopen) and every enc_len fits its slot, so no sum below can wrap
     const uint64_t shift = a.gather ? base0 : 0;
     if (tid == 0) {
@@ -1698,14 +1746,7 @@ __global__ __launch_bounds__(kScan) void seg_aseal_kernel(AppCall a)
         carry += total;
     }
     __syncthreads();
-    if (tid != 0) return;
-    const uint64_t end = s_end;
-    const bool fits = end <= a.out_cap;
-    *a.status_out = fits ? 0 : HC_ERR_CAPACITY;
-    *a.out_len = end;
-    if (a.bad_segment) *a.bad_segment = kNoSeg;
-    w.ctl[0] = fits ? 1 : 0;
-    w.ctl[1] = end - shift;
+    if (tid == 0) seal_fits(w, a.o, a.out_cap, s_end, s_end - shift);
 }
 
 // The new header and index in front of the spliced bytes: header words 0 .. 5 (raw_len and
@@ -1714,7 +1755,7 @@ __global__ __launch_bounds__(kScan) void seg_aseal_kernel(AppCall a)
 // entries from the seal's arrays; then the zero padding up to the first segment.
 __global__ __launch_bounds__(256) void seg_aindex_kernel(AppCall a)
 {
-    const AppWs &w = a.w;
+    const CodedWs &w = a.w.co;
     if (w.ctl[0] == 0) return;  // not sealed: nothing is written
     const uint64_t *i64 = reinterpret_cast<const uint64_t *>(a.in);
     const uint32_t *i32 = reinterpret_cast<const uint32_t *>(a.in);
@@ -1723,11 +1764,12 @@ __global__ __launch_bounds__(256) void seg_aindex_kernel(AppCall a)
     const uint64_t idx_end = index_end(a.new_n, a.check != 0);
     if (blockIdx.x == 0 && threadIdx.x >= 8 && threadIdx.x < 14) {
         const uint32_t t = threadIdx.x - 8;
-        o64[t] = t == 0 ? a.magic : t == 1 ? a.flags : t == 2 ? a.new_raw : t == 3 ? a.seg_bytes : t == 4 ? a.width : a.new_n;
+        o64[t] = t == 0 ? a.h.magic : t == 1 ? a.h.flags : t == 2 ? a.new_raw : t == 3 ? a.h.seg_bytes
+                 : t == 4 ? a.h.width : a.new_n;
     }
     for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < a.new_n; k += (uint64_t)gridDim.x * 256) {
         o64[6 + k] = k < a.K ? i64[6 + k] : w.enc_lens[k - a.K];
-        if (a.check) o32[12 + 2 * a.new_n + k] = k < a.K ? i32[12 + 2 * a.n + k] : w.crc[k - a.K];
+        if (a.check) o32[12 + 2 * a.new_n + k] = k < a.K ? i32[12 + 2 * a.h.n + k] : w.crc[k - a.K];
     }
     if (blockIdx.x == 0 && threadIdx.x < (align16(idx_end) - idx_end) / 4) o32[idx_end / 4 + threadIdx.x] = 0;
 }
@@ -1736,8 +1778,7 @@ __global__ __launch_bounds__(256) void seg_aindex_kernel(AppCall a)
 struct AppSizes {
     Cuts c;
     AppPlan p;
-    uint64_t cap_full, cap_last, slot_full, slot_bytes, awork_bytes;
-    bool adapt, check;
+    CodedSizes co;
 };
 // HC_OK, or the status that the host decides (HC_ERR_ARG, HC_ERR_MATRIX_SIZE). dec_in: the decoded
 // segment's stream length when the host knows it (the host call); null: the longest stream this
@@ -1745,28 +1786,20 @@ struct AppSizes {
 int app_sizes(const hc_seg_info_t &info, uint64_t in_len, uint64_t add_len, const uint64_t *dec_in, AppSizes &s)
 {
     (void)info_ok(info, in_len, s.c);
-    s.adapt = (info.flags & HC_FLAG_ADAPT) != 0;
-    s.check = checked(info.flags);
-    const int rc = hc_seg_index::append_plan(s.c, info.raw_len, add_len, info.seg_bytes, s.adapt, info.width, &s.p);
+    const bool adapt = (info.flags & HC_FLAG_ADAPT) != 0;
+    const int rc = hc_seg_index::append_plan(s.c, info.raw_len, add_len, info.seg_bytes, adapt, info.width, &s.p);
     if (rc) return rc;
     if (s.p.coded > kMaxSegs) return HC_ERR_ARG;
-    s.cap_full = hc_compress_bound(s.c.full, s.adapt);
-    s.cap_last = hc_compress_bound(s.p.nc.last, s.adapt);
-    s.slot_full = align16(s.cap_full);
-    s.slot_bytes = hc_seg_index::append_slots(s.p, s.slot_full, align16(s.cap_last));
-    s.awork_bytes = 0;
-    if (s.adapt) {
-        const uint64_t old_bound = hc_compress_bound(s.c.last, 1);
-        const uint64_t din = dec_in ? *dec_in : (in_len < old_bound ? in_len : old_bound);
-        const uint64_t e = s.p.coded ? hc::adapt_encode_work_bound(s.p.stage, (uint32_t)s.p.coded) : 0;
-        const uint64_t d = s.p.decoded ? hc::adapt_decode_work_bound(din, s.c.last, 1) : 0;
-        s.awork_bytes = e > d ? e : d;  // the decode launch is over before the encode launch starts
-    }
+    s.co = coded_sizes(info, s.c.full, s.p.nc.last);
+    s.co.slot_bytes = hc_seg_index::append_slots(s.p, s.co.slot_full, align16(s.co.cap_last));
+    const uint64_t old_bound = hc_compress_bound(s.c.last, 1);
+    const uint64_t din = dec_in ? *dec_in : (in_len < old_bound ? in_len : old_bound);
+    s.co.awork_bytes = coded_awork(adapt, s.p.coded, s.p.stage, s.p.decoded, din, s.c.last);
     return HC_OK;
 }
 AppWs app_ws(void *work, const AppSizes &s)
 {
-    return carve_app(work, s.p.coded, s.check, s.p.stage, s.slot_bytes, s.awork_bytes);
+    return carve_app(work, s.p.coded, s.co.check, s.p.stage, s.co.slot_bytes, s.co.awork_bytes);
 }
 
 // hc_seg_append_dev, and the host call's device part (gather; `in` is then its compact upload and
@@ -1795,46 +1828,25 @@ int append_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, co
     if (work_bytes < w.total) return HC_ERR_ARG;
     const uint64_t C = s.p.coded, D = s.p.decoded;
     const AppCall a{in, out, in_len, out_cap, skip,
-                    get64(kMagic), info->flags & 0xFFFFu, info->raw_len, info->seg_bytes, info->width, c.n,
+                    HeaderWords{get64(kMagic), info->flags & 0xFFFFu, info->raw_len, info->seg_bytes, info->width, c.n},
                     c.full, c.last, info->raw_len + add_len, s.p.nc.n, s.p.nc.last,
-                    s.p.K, C, D, s.p.tail, add_len, s.slot_full, s.cap_full, s.cap_last,
-                    s.check ? 1u : 0u, gather ? 1u : 0u, w, out_len, bad_segment, status};
+                    s.p.K, C, D, s.p.tail, add_len, s.co.slot_full, s.co.cap_full, s.co.cap_last,
+                    s.co.check ? 1u : 0u, gather ? 1u : 0u, w, WriteOut{out_len, bad_segment, status}};
 
     seg_aopen_kernel<<<1, kScan, 0, st>>>(a);
     HC_CK(hipGetLastError());
-    if (D) {
-        Batch b{in, w.d_in_off, w.d_in_len, 1, w.stage, w.d_out_off, w.d_out_cap, w.d_out_len, w.d_status, 0};
-        if (s.adapt) HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
-        else HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
-        if (s.check)
-            HC_CK(hc::launch_crc32(w.stage, w.d_out_off, w.d_out_cap, 1, w.d_crc, hc::CrcGate{w.d_status, w.d_out_len}, st));
-    }
+    if (decode_to_stage(in, w.co, D, s.co, st) != HC_OK) return HC_ERR_DEVICE;
     if (C) {
         seg_aplan_kernel<<<(uint32_t)((C + 255) / 256), 256, 0, st>>>(a);
         HC_CK(hipGetLastError());
-        // the added bytes behind the open tail, one range per coded entry, at any byte alignment
-        HC_CK(hc::launch_pack(add, w.pk_src, w.pk_len, (uint32_t)C, w.stage, w.pk_dst, st));
-        Batch b{w.stage, w.in_offs, w.in_lens, (uint32_t)C, w.slots, w.slot_offs, w.slot_caps, w.enc_lens, w.status,
-                info->flags & HC_FLAG_DIFF};
-        if (s.check) HC_CK(hc::launch_crc32(w.stage, w.in_offs, w.in_lens, C, w.crc, hc::CrcGate{nullptr, nullptr}, st));
-        if (s.adapt) HC_CK(hc::adapt_encode_batch(b, w.widths, w.awork, w.awork_bytes, st));
-        else HC_CK(hc::launch_encode(b, (info->flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
     }
+    // the added bytes behind the open tail, one range per coded entry
+    if (code_from_stage(add, w.pk_src, w.pk_len, w.pk_dst, (uint32_t)C, w.co, C, s.co, info->flags, st) != HC_OK)
+        return HC_ERR_DEVICE;
     seg_aseal_kernel<<<1, kScan, 0, st>>>(a);
-    // the range write's splice over the seal's pieces (it reads these fields alone); the grid by the
-    // longest result there can be
-    UpdCall u{};
-    u.in = in;
-    u.out = out;
-    u.C = C;
-    u.w.pc_src = w.pc_src;
-    u.w.pc_dst = w.pc_dst;
-    u.w.pc_len = w.pc_len;
-    u.w.ctl = w.ctl;
-    u.w.slots = w.slots;
-    const uint64_t longest = gather ? s.slot_bytes : hc_seg_index::append_bound(s.p, in_len, c.n, s.check, s.slot_bytes);
-    const uint64_t tiles = longest / (4096ull * kSpliceChunks) + 1;
-    seg_usplice_kernel<<<(uint32_t)(tiles < 4096 ? tiles : 4096), 256, 0, st>>>(u);  // (the rest by stride)
+    const uint64_t longest =
+        gather ? s.co.slot_bytes : hc_seg_index::append_bound(s.p, in_len, c.n, s.co.check, s.co.slot_bytes);
+    launch_splice(in, out, w.co, C, longest, st);
     if (!gather) {
         const uint64_t blocks = (s.p.nc.n + 255) / 256;
         seg_aindex_kernel<<<(uint32_t)(blocks < 65536 ? blocks : 65536), 256, 0, st>>>(a);
@@ -1996,13 +2008,8 @@ int hc_seg_decompress_range(const uint8_t *in, uint64_t in_len, uint64_t offset,
                             uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment)
 {
     if ((!in && in_len) || !out_len || (!out && out_cap)) return HC_ERR_ARG;
-    auto fail = [&](int rc, uint64_t len) {
-        *out_len = len;
-        if (bad_segment) *bad_segment = kNoSeg;
-        return rc;
-    };
     hc_seg_info_t info;
-    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0);
+    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0, out_len, bad_segment);
     if (!range_ok(info.raw_len, offset, length)) return HC_ERR_ARG;
     Cuts c;
     (void)info_ok(info, in_len, c);
@@ -2012,10 +2019,10 @@ int hc_seg_decompress_range(const uint8_t *in, uint64_t in_len, uint64_t offset,
     const bool check = checked(info.flags);
     const uint64_t idx = align16(index_end(c.n, check));
     if (hc_seg_index::index_scan(in, in_len, c.n, check, range_cover(c, offset, length), &s0, &s1) != HC_OK)
-        return fail(HC_ERR_SEG_HEADER, 0);
-    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0);
-    if (out_cap < length) return fail(HC_ERR_CAPACITY, length);
-    (void)fail(HC_OK, 0);  // (what a HIP error below leaves behind)
+        return fail(HC_ERR_SEG_HEADER, 0, out_len, bad_segment);
+    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0, out_len, bad_segment);
+    if (out_cap < length) return fail(HC_ERR_CAPACITY, length, out_len, bad_segment);
+    (void)fail(HC_OK, 0, out_len, bad_segment);  // (what a HIP error below leaves behind)
     // the compact upload: header and index [0, idx), then the span; in_len stays the container's
     const uint64_t span = s1 - s0;
     const uint64_t wb = single_work_bound(info, in_len, offset, length, false, span);
@@ -2031,14 +2038,9 @@ int hc_seg_decompress_range(const uint8_t *in, uint64_t in_len, uint64_t offset,
     const int rc = decode_dev(din.as<uint8_t>(), in_len, &info, offset, length, false, dout.as<uint8_t>(), length, m,
                               reinterpret_cast<int32_t *>(m + 1), m + 2, work.p, wb, st, s0 - idx, span);
     if (rc) return rc;
-    uint64_t h[4] = {0, 0, 0, 0};
-    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    HC_CK(hipStreamSynchronize(st));
-    const int status = (int32_t)(uint32_t)h[1];
-    *out_len = h[0];
-    if (bad_segment) *bad_segment = h[2];
+    const int status = read_verdict(meta, st, out_len, bad_segment);
     if (status) return status;
-    if (h[0]) HC_CK(hipMemcpy(out, dout.p, h[0], hipMemcpyDeviceToHost));
+    if (*out_len) HC_CK(hipMemcpy(out, dout.p, *out_len, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 
@@ -2061,7 +2063,7 @@ uint64_t hc_seg_update_bound(const hc_seg_info_t *info, uint64_t in_len, const h
     if (!info) return 0;
     Cuts c;
     if (!info_ok(*info, in_len, c) || !hc_seg_index::patches_ok(info->raw_len, patches, n_patches, nullptr)) return 0;
-    return sat_add(in_len, upd_sizes(*info, in_len, patches, n_patches, nullptr).slot_bytes);
+    return sat_add(in_len, upd_sizes(*info, in_len, patches, n_patches, nullptr).co.slot_bytes);
 }
 
 uint64_t hc_seg_update_work_bound(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_patch_t *patches,
@@ -2103,9 +2105,9 @@ int hc_seg_update_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *i
     if (work_bytes < w.total) return HC_ERR_ARG;
     const uint64_t P = n_patches, D = s.u.decoded, C = s.u.covered;
     const UpdCall a{in, out, in_len, out_cap,
-                    get64(kMagic), info->flags & 0xFFFFu, info->raw_len, info->seg_bytes, info->width, c.n,
-                    c.full, c.last, s.slot_full, s.cap_full, s.cap_last,
-                    P, D, C, s.check ? 1u : 0u, w, out_len, bad_segment, status};
+                    HeaderWords{get64(kMagic), info->flags & 0xFFFFu, info->raw_len, info->seg_bytes, info->width, c.n},
+                    c.full, c.last, s.co.slot_full, s.co.cap_full, s.co.cap_last,
+                    P, D, C, s.co.check ? 1u : 0u, w, WriteOut{out_len, bad_segment, status}};
 
     for (uint64_t base = 0; base < P; base += kPatchChunk) {
         PatchChunk ch;
@@ -2122,26 +2124,13 @@ int hc_seg_update_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *i
     if (C) seg_uplan_kernel<<<(uint32_t)((C + 255) / 256), 256, 0, st>>>(a);
     seg_uopen_kernel<<<1, kScan, 0, st>>>(a);
     HC_CK(hipGetLastError());
-    if (D) {
-        Batch b{in, w.d_in_offs, w.d_in_lens, (uint32_t)D, w.stage, w.d_out_offs, w.d_out_caps, w.d_out_lens, w.d_status, 0};
-        if (s.adapt) HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
-        else HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
-        if (s.check)
-            HC_CK(hc::launch_crc32(w.stage, w.d_out_offs, w.d_out_caps, D, w.d_crc, hc::CrcGate{w.d_status, w.d_out_lens}, st));
-    }
-    if (C) {
-        // every patch's bytes over the staging region, at any byte alignment (an empty patch costs nothing)
-        HC_CK(hc::launch_pack(patch_data, w.pk_src, w.pk_len, n_patches, w.stage, w.pk_dst, st));
-        Batch b{w.stage, w.in_offs, w.in_lens, (uint32_t)C, w.slots, w.slot_offs, w.slot_caps, w.enc_lens, w.status,
-                info->flags & HC_FLAG_DIFF};
-        if (s.check) HC_CK(hc::launch_crc32(w.stage, w.in_offs, w.in_lens, C, w.crc, hc::CrcGate{nullptr, nullptr}, st));
-        if (s.adapt) HC_CK(hc::adapt_encode_batch(b, w.widths, w.awork, w.awork_bytes, st));
-        else HC_CK(hc::launch_encode(b, (info->flags & HC_FLAG_DIFF) ? hc::SRC_RAW_DIFF : hc::SRC_RAW, st));
-    }
+    if (decode_to_stage(in, w.co, D, s.co, st) != HC_OK) return HC_ERR_DEVICE;
+    // every patch's bytes over the covered segments' raw bytes
+    if (code_from_stage(patch_data, w.pk_src, w.pk_len, w.pk_dst, n_patches, w.co, C, s.co, info->flags, st) != HC_OK)
+        return HC_ERR_DEVICE;
     seg_useal_kernel<<<1, kScan, 0, st>>>(a);
-    // the grid by the longest result there can be: the old container and every slot filled
-    const uint64_t tiles = (in_len + s.slot_bytes) / (4096ull * kSpliceChunks) + 1;
-    seg_usplice_kernel<<<(uint32_t)(tiles < 4096 ? tiles : 4096), 256, 0, st>>>(a);  // (the rest by stride)
+    // the longest result there can be: the old container and every slot filled
+    launch_splice(in, out, w.co, C, in_len + s.co.slot_bytes, st);
     if (C) seg_uindex_kernel<<<(uint32_t)((C + 255) / 256), 256, 0, st>>>(a);
     HC_CK(hipGetLastError());
     return HC_OK;
@@ -2153,23 +2142,18 @@ int hc_seg_update(const uint8_t *in, uint64_t in_len, const hc_seg_patch_t *patc
 {
     if ((!in && in_len) || !out_len || (!out && out_cap)) return HC_ERR_ARG;
     if ((!patches && n_patches) || (!patch_data && patch_data_len)) return HC_ERR_ARG;
-    auto fail = [&](int rc, uint64_t len) {
-        *out_len = len;
-        if (bad_segment) *bad_segment = kNoSeg;
-        return rc;
-    };
     hc_seg_info_t info;
-    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0);
+    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0, out_len, bad_segment);
     if (!hc_seg_index::patches_ok(info.raw_len, patches, n_patches, &patch_data_len)) return HC_ERR_ARG;
     const UpdSizes s = upd_sizes(info, in_len, patches, n_patches, nullptr);
     if (s.u.covered > kMaxSegs) return HC_ERR_ARG;
     uint64_t s0 = 0, s1 = 0;
-    if (hc_seg_index::index_scan(in, in_len, s.c.n, s.check, Cover{0, 0}, &s0, &s1) != HC_OK)
-        return fail(HC_ERR_SEG_HEADER, 0);
-    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0);
-    (void)fail(HC_OK, 0);  // (what a HIP error below leaves behind)
+    if (hc_seg_index::index_scan(in, in_len, s.c.n, s.co.check, Cover{0, 0}, &s0, &s1) != HC_OK)
+        return fail(HC_ERR_SEG_HEADER, 0, out_len, bad_segment);
+    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0, out_len, bad_segment);
+    (void)fail(HC_OK, 0, out_len, bad_segment);  // (what a HIP error below leaves behind)
     // the whole container and every patch byte go up, the whole result comes down
-    const uint64_t bound = sat_add(in_len, s.slot_bytes), cap = out_cap < bound ? out_cap : bound;
+    const uint64_t bound = sat_add(in_len, s.co.slot_bytes), cap = out_cap < bound ? out_cap : bound;
     const uint64_t wb = upd_ws(nullptr, s, n_patches).total;
     hipStream_t st = nullptr;
     DevBuf din, dpatch, dout, work, meta;
@@ -2185,14 +2169,9 @@ int hc_seg_update(const uint8_t *in, uint64_t in_len, const hc_seg_patch_t *patc
                                      patch_data_len, dout.as<uint8_t>(), cap, m, reinterpret_cast<int32_t *>(m + 1), m + 2,
                                      work.p, wb, st);
     if (rc) return rc;
-    uint64_t h[4] = {0, 0, 0, 0};
-    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    HC_CK(hipStreamSynchronize(st));
-    const int status = (int32_t)(uint32_t)h[1];
-    *out_len = h[0];
-    if (bad_segment) *bad_segment = h[2];
+    const int status = read_verdict(meta, st, out_len, bad_segment);
     if (status) return status;
-    if (h[0]) HC_CK(hipMemcpy(out, dout.p, h[0], hipMemcpyDeviceToHost));
+    if (*out_len) HC_CK(hipMemcpy(out, dout.p, *out_len, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 
@@ -2220,7 +2199,7 @@ uint64_t hc_seg_append_bound(const hc_seg_info_t *info, uint64_t in_len, uint64_
     Cuts c;
     AppSizes s;
     if (!info_ok(*info, in_len, c) || app_sizes(*info, in_len, add_len, nullptr, s) != HC_OK) return 0;
-    return hc_seg_index::append_bound(s.p, in_len, c.n, s.check, s.slot_bytes);
+    return hc_seg_index::append_bound(s.p, in_len, c.n, s.co.check, s.co.slot_bytes);
 }
 
 uint64_t hc_seg_append_work_bound(const hc_seg_info_t *info, uint64_t in_len, uint64_t add_len)
@@ -2245,13 +2224,8 @@ int hc_seg_append(const uint8_t *in, uint64_t in_len, const uint8_t *add, uint64
                   uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment)
 {
     if ((!in && in_len) || !out_len || (!out && out_cap) || (!add && add_len)) return HC_ERR_ARG;
-    auto fail = [&](int rc, uint64_t len) {
-        *out_len = len;
-        if (bad_segment) *bad_segment = kNoSeg;
-        return rc;
-    };
     hc_seg_info_t info;
-    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0);
+    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0, out_len, bad_segment);
     AppSizes s;
     {
         const int rc = app_sizes(info, in_len, add_len, nullptr, s);
@@ -2259,20 +2233,21 @@ int hc_seg_append(const uint8_t *in, uint64_t in_len, const uint8_t *add, uint64
     }
     // The index on the host: the verdict without a device, and the kept block's last byte. Old segment
     // n - 1, when it is not kept, starts at the next multiple of 16 and ends with the container.
+    const bool check = s.co.check;
     const uint64_t n = s.c.n, K = s.p.K, C = s.p.coded;
-    const uint64_t first = align16(index_end(n, s.check)), new_first = align16(index_end(s.p.nc.n, s.check));
+    const uint64_t first = align16(index_end(n, check)), new_first = align16(index_end(s.p.nc.n, check));
     uint64_t s0 = 0, kept_end = 0;
-    if (hc_seg_index::index_scan(in, in_len, n, s.check, K ? Cover{K - 1, 1} : Cover{0, 0}, &s0, &kept_end) != HC_OK)
-        return fail(HC_ERR_SEG_HEADER, 0);
-    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0);
+    if (hc_seg_index::index_scan(in, in_len, n, check, K ? Cover{K - 1, 1} : Cover{0, 0}, &s0, &kept_end) != HC_OK)
+        return fail(HC_ERR_SEG_HEADER, 0, out_len, bad_segment);
+    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0, out_len, bad_segment);
     if (K == 0) kept_end = first;
     const uint64_t kept_len = kept_end - first;
     if (C == 0) {  // nothing is added: the input container
-        if (in_len > out_cap) return fail(HC_ERR_CAPACITY, in_len);
+        if (in_len > out_cap) return fail(HC_ERR_CAPACITY, in_len, out_len, bad_segment);
         memcpy(out, in, in_len);
-        return fail(HC_OK, in_len);
+        return fail(HC_OK, in_len, out_len, bad_segment);
     }
-    (void)fail(HC_OK, 0);  // (what a HIP error below leaves behind)
+    (void)fail(HC_OK, 0, out_len, bad_segment);  // (what a HIP error below leaves behind)
     // The compact upload: header and index [0, first), then old segment n - 1's stream when it is
     // decoded; in_len stays the container's. The kept bytes never leave the host.
     const uint64_t last_off = K == n ? in_len : align16(kept_end);
@@ -2286,7 +2261,7 @@ int hc_seg_append(const uint8_t *in, uint64_t in_len, const uint8_t *add, uint64
     DevBuf din, dadd, dout, work, meta;
     HC_CK(din.alloc(first + dec_in + 16));
     HC_CK(dadd.alloc(add_len + 16));
-    HC_CK(dout.alloc(s.slot_bytes + 16));
+    HC_CK(dout.alloc(s.co.slot_bytes + 16));
     HC_CK(work.alloc(wb));
     HC_CK(meta.alloc(32));
     HC_CK(hipMemcpyAsync(din.p, in, first, hipMemcpyHostToDevice, st));
@@ -2296,33 +2271,28 @@ int hc_seg_append(const uint8_t *in, uint64_t in_len, const uint8_t *add, uint64
     const int rc = append_dev(din.as<uint8_t>(), in_len, &info, dadd.as<uint8_t>(), add_len, dout.as<uint8_t>(), out_cap, m,
                               reinterpret_cast<int32_t *>(m + 1), m + 2, work.p, wb, st, true, last_off - first, &dec_in);
     if (rc) return rc;
-    uint64_t h[4] = {0, 0, 0, 0};
-    HC_CK(hipMemcpyAsync(h, meta.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    HC_CK(hipStreamSynchronize(st));
-    const int status = (int32_t)(uint32_t)h[1];
-    *out_len = h[0];
-    if (bad_segment) *bad_segment = h[2];
+    const int status = read_verdict(meta, st, out_len, bad_segment);
     if (status) return status;
     // the result on the host: header, index, the kept block from `in`, the coded streams as gathered
-    const AppWs w = app_ws(work.p, s);
-    const uint64_t new_n = s.p.nc.n, base = new_first + align16(kept_len), gathered = h[0] - base;
+    const CodedWs w = app_ws(work.p, s).co;
+    const uint64_t new_n = s.p.nc.n, base = new_first + align16(kept_len), gathered = *out_len - base;
     std::vector<uint64_t> lens(C);
-    std::vector<uint32_t> crcs(s.check ? C : 0);
+    std::vector<uint32_t> crcs(check ? C : 0);
     HC_CK(hipMemcpyAsync(lens.data(), w.enc_lens, 8 * C, hipMemcpyDeviceToHost, st));
-    if (s.check) HC_CK(hipMemcpyAsync(crcs.data(), w.crc, 4 * C, hipMemcpyDeviceToHost, st));
+    if (check) HC_CK(hipMemcpyAsync(crcs.data(), w.crc, 4 * C, hipMemcpyDeviceToHost, st));
     HC_CK(hipMemcpyAsync(out + base, dout.p, gathered, hipMemcpyDeviceToHost, st));
     memcpy(out, in, 16);
     const uint64_t words[4] = {info.raw_len + add_len, info.seg_bytes, info.width, new_n};
     memcpy(out + 16, words, 32);
     memcpy(out + 48, in + 48, 8 * K);
-    if (s.check) memcpy(out + 48 + 8 * new_n, in + 48 + 8 * n, 4 * K);
-    const uint64_t idx_end = index_end(new_n, s.check);
+    if (check) memcpy(out + 48 + 8 * new_n, in + 48 + 8 * n, 4 * K);
+    const uint64_t idx_end = index_end(new_n, check);
     memset(out + idx_end, 0, new_first - idx_end);
     memcpy(out + new_first, in + first, kept_len);
     memset(out + new_first + kept_len, 0, base - (new_first + kept_len));
     HC_CK(hipStreamSynchronize(st));
     memcpy(out + 48 + 8 * K, lens.data(), 8 * C);
-    if (s.check) memcpy(out + 48 + 8 * new_n + 4 * K, crcs.data(), 4 * C);
+    if (check) memcpy(out + 48 + 8 * new_n + 4 * K, crcs.data(), 4 * C);
     return HC_OK;
 }
 

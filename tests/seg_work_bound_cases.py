@@ -1,5 +1,6 @@
 """The argument table of tests/test_seg_work_bounds.py: every public work bound of the segmented
-container (hc_seg_*_work_bound*) over small arguments, as `key -> thunk` pairs. The bounds are host
+container (hc_seg_*_work_bound*, and the write calls' output bounds hc_seg_update_bound and
+hc_seg_append_bound beside theirs) over small arguments, as `key -> thunk` pairs. The bounds are host
 arithmetic: no call here needs a device. tests/golden/make_seg_work_bounds.py records the values."""
 import ctypes
 
@@ -50,6 +51,78 @@ def _copy(info, **changes):
     return c
 
 
+def _full(info):
+    """the cut of every segment but the last"""
+    return max(8, (info.seg_bytes // WIDTH) & ~3) * WIDTH if info.flags & ADAPT else info.seg_bytes
+
+
+def _patch_lists(info):
+    """{name: [(offset, length, src_off)]} for a range write: no segment, one in part, one whole,
+    several with the last one among them (an adaptive container's last cut may be longer than
+    `full`: there "tail" covers the last segment in part)"""
+    raw, full = info.raw_len, _full(info)
+    p = {"none": [], "empty": [(raw // 2, 0, 0)]}
+    if raw:
+        p["partial"] = [(raw // 3, 1, 0)]
+        p["whole"] = [(0, min(full, raw), 0)]
+    if raw > 2:
+        spans = [(0, 1)]
+        if raw > 2 * full + 2:  # across a cut, behind the first patch's segment
+            spans.append((2 * full - 1, 2))
+        spans.append((raw - 1, 1))
+        at, p["several"] = 0, []
+        for o, m in spans:
+            p["several"].append((o, m, at))
+            at += m
+    if raw > full:  # the last segment whole and the one before it in part
+        last = (raw - 1) // full * full
+        p["tail"] = [(last - 1, raw - last + 1, 0)]
+    return p
+
+
+def _add_lens(info):
+    """0, 1, 16 (in an adaptive container, whose rows are whole: one that the call refuses, 1 row
+    and 16 rows), one that closes the last cut exactly, and one that leaves an open tail behind it"""
+    full, unit = _full(info), WIDTH if info.flags & ADAPT else 1
+    close = -info.raw_len % full or full
+    return [0, 1, unit, 16 * unit, close, close + full + unit]
+
+
+def _write_cases(hc, out, name, info, clen):
+    """the four bounds of the write calls (range write, append) over one container"""
+    L = hc.lib()
+    for pname, tri in _patch_lists(info).items():
+        arr = hc.seg_patches(tri)
+        out[f"update_bound {name} {pname}"] = (
+            lambda info=info, arr=arr, k=len(tri): L.hc_seg_update_bound(ctypes.byref(info), clen, arr, k))
+        out[f"update_work {name} {pname}"] = (
+            lambda info=info, arr=arr, k=len(tri): L.hc_seg_update_work_bound(ctypes.byref(info), clen, arr, k))
+    for add in _add_lens(info):
+        out[f"append_bound {name} add={add}"] = (
+            lambda info=info, add=add: L.hc_seg_append_bound(ctypes.byref(info), clen, add))
+        out[f"append_work {name} add={add}"] = (
+            lambda info=info, add=add: L.hc_seg_append_work_bound(ctypes.byref(info), clen, add))
+    if info.raw_len != 17:
+        return
+    # arguments that the calls refuse (0), and an info that fails the rules (16: no workspace; no bound)
+    refused = {"unsorted": [(8, 2, 0), (0, 2, 2)], "overlap": [(0, 4, 0), (3, 2, 4)],
+               "outside": [(info.raw_len, 1, 0)], "length wraps": [(1, 2**64 - 1, 0)]}
+    for pname, tri in refused.items():
+        arr = hc.seg_patches(tri)
+        out[f"update_bound {name} {pname}"] = (
+            lambda info=info, arr=arr, k=len(tri): L.hc_seg_update_bound(ctypes.byref(info), clen, arr, k))
+        out[f"update_work {name} {pname}"] = (
+            lambda info=info, arr=arr, k=len(tri): L.hc_seg_update_work_bound(ctypes.byref(info), clen, arr, k))
+    out[f"append_bound {name} add wraps"] = lambda info=info: L.hc_seg_append_bound(ctypes.byref(info), clen, 2**64 - 1)
+    out[f"append_work {name} add wraps"] = lambda info=info: L.hc_seg_append_work_bound(ctypes.byref(info), clen, 2**64 - 1)
+    bad = _copy(info, n_segments=info.n_segments + 1)
+    one = hc.seg_patches([(0, 1, 0)])
+    out[f"update_bound {name} bad info"] = lambda bad=bad: L.hc_seg_update_bound(ctypes.byref(bad), clen, one, 1)
+    out[f"update_work {name} bad info"] = lambda bad=bad: L.hc_seg_update_work_bound(ctypes.byref(bad), clen, one, 1)
+    out[f"append_bound {name} bad info"] = lambda bad=bad: L.hc_seg_append_bound(ctypes.byref(bad), clen, 1)
+    out[f"append_work {name} bad info"] = lambda bad=bad: L.hc_seg_append_work_bound(ctypes.byref(bad), clen, 1)
+
+
 def cases(hc):
     """{key: thunk}: each thunk calls one bound"""
     L = hc.lib()
@@ -67,6 +140,7 @@ def cases(hc):
         pool = _containers(hc, seg) if seg else []  # (0 is 65536: the same containers)
         dec_items = []  # (name, info, length, offset, length of the range)
         for name, info, clen in pool:
+            _write_cases(hc, out, name, info, clen)
             out[f"decompress {name}"] = (
                 lambda info=info, clen=clen: L.hc_seg_decompress_work_bound(ctypes.byref(info), clen))
             if info.raw_len == 17:  # an info that fails the rules: no workspace

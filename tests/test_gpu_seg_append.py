@@ -103,6 +103,22 @@ def test_matches_model(hc, gpu, case):
         assert hc.seg_append(c, bytes(w + 1), full=True, cap=4096)[0] == hc.HC_ERR_MATRIX_SIZE
 
 
+@pytest.mark.parametrize("check", (False, True), ids=("plain", "checked"))
+def test_coded_entries_across_a_scan_tile(hc, gpu, check):
+    """more coded segments than the seal scans in one tile, behind a decoded open tail of one byte;
+    the device call and the host call (which gathers the coded streams alone)"""
+    case = ("rng:256:17", False, 512, 16, False, check)
+    name, adapt, w, seg, diff, check = case
+    raw, c, f, rs = srm.built(case)
+    t = sam.add_bytes(16 * 1030)
+    st, K, new, dec = sam.plan(f, len(t))
+    assert (st, K, dec) == (0, 1, 1) and len(new) - K == 1031 > 1024
+    want = sam.append(c, t)
+    assert want[0] == 0
+    both(hc, gpu, c, t, want)
+    assert hc.seg_compress(raw + t, diff, adapt, w, seg, check=check) == (0, want[2])
+
+
 def test_chain(hc, gpu):
     """three appends of unequal lengths from the empty container: one ends inside a segment, one on
     a cut, one spans three segments; the result is one seg_compress of the concatenation"""

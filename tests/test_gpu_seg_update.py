@@ -26,6 +26,11 @@ PHOTO_M = [c for c in srm.CASES if c[0] == "photo:64:200" and c[4]]
 PHOTO_MK = [c for c in PHOTO_M if c[5]]
 BIG_CASE = (f"rng:256:{srm.BIG}", False, 512, 16, True, False)
 EDGES = (4100, 8192)   # segments 1 .. 3: 1 and 3 decoded, 2 covered whole
+# the seal's piece scan past one 1024-entry tile: 520 segments covered in part by one byte each (1041
+# pieces, 11 descriptor launches, a segment in every old block between them), and 520 covered whole by
+# one patch (nothing decoded, empty old blocks between them)
+TILE_CASES = [(f"rng:256:{srm.BIG}", False, 512, 16, False, k) for k in (False, True)]
+TILE_SETS = {"partial_520": [(32 * i + 3, 1) for i in range(520)], "whole_520": [(16 * 700, 16 * 520)]}
 
 
 def _upload(torch, data, front=0):
@@ -99,6 +104,25 @@ def test_matches_model(hc, gpu, case):
             if spans == [(0, len(raw))]:  # nothing is decoded: the encoder's own output for the patch
                 assert sup.plan(f, sup.triples(patches)[0])[1] == []
                 assert hc.seg_compress(new_raw, diff, adapt, w, seg, check=check) == (0, want[2]), (sname, kind)
+
+
+@pytest.mark.parametrize("sname", TILE_SETS)
+@pytest.mark.parametrize("case", TILE_CASES, ids=srm.case_id)
+def test_pieces_across_a_scan_tile(hc, gpu, case, sname):
+    """more pieces than the seal scans in one tile: 520 covered segments are 1041 pieces"""
+    name, adapt, w, seg, diff, check = case
+    raw, c, f, rs = srm.built(case)
+    tri = [(o, m, 0) for o, m in TILE_SETS[sname]]
+    covered, decoded = sup.plan(f, tri)
+    assert len(covered) == 520 and 2 * len(covered) + 1 > 1024
+    assert len(decoded) == (520 if sname == "partial_520" else 0)
+    # every old block between two covered segments holds a segment, or none does
+    assert all(b - a == (2 if sname == "partial_520" else 1) for a, b in zip(covered, covered[1:]))
+    patches = sup.fill(TILE_SETS[sname], "random")
+    want = sup.update(c, patches)
+    assert want[0] == 0
+    both(hc, gpu, c, patches, want)
+    assert hc.seg_compress(sup.patched(raw, patches), diff, adapt, w, seg, check=check) == (0, want[2])
 
 
 @pytest.mark.parametrize("case", PHOTO_M, ids=srm.case_id)

@@ -1,5 +1,6 @@
 """Every public work bound of the segmented container (hc_seg_compress_work_bound{,2},
-hc_seg_decompress_work_bound, hc_seg_decompress_range_work_bound, hc_seg_*_batch_work_bound) returns
+hc_seg_decompress_work_bound, hc_seg_decompress_range_work_bound, hc_seg_*_batch_work_bound,
+hc_seg_update_work_bound, hc_seg_append_work_bound, and the output bounds of the last two) returns
 what it returned at the commit named in tests/golden/seg_work_bounds.json: callers size their
 workspaces by these, and the single and batch calls carve theirs with shared code. Host arithmetic,
 no device."""
