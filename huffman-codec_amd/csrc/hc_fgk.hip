@@ -40,7 +40,7 @@ namespace hc {
 #define HC_DEBUG_HOOKS 1
 #endif
 // the most codes one decoder batch step takes (a multiple of 4 up to 24; described with the
-// decoder's other knobs below)
+// decoder's other knobs below, HC_DEC_CHAIN -- how the step finds their starts -- among them)
 #ifndef HC_DEC_PACK
 #define HC_DEC_PACK 16
 #endif
@@ -255,6 +255,22 @@ static_assert(HC_ENC_MISS_RUN_MAX >= 1 && HC_ENC_MISS_RUN_MAX <= 15, "a run lies
 #ifndef HC_DEC_BATCH
 #define HC_DEC_BATCH 7
 #endif
+// HC_DEC_CHAIN (1, 2 or 4): the stride of the packed step's serial chain of code starts. 1: one
+// link (lane read, add, lane write) per code, up to HC_DEC_PACK of them. 2 / 4: the depth map is
+// composed with itself once / twice, lane-parallel (dep2[o] = dep[o] + dep[o + dep[o]], one
+// ds_bpermute each), the chain visits every second / fourth start, and the starts in between are
+// filled in afterwards, lane-parallel again (one DPP move, one ds_bpermute, an add and a min per
+// level). Built after the HC_DEC_EXIT8 exit, so a step that leaves there pays nothing. The step
+// takes the same codes whatever the stride (model: tests/fgk_chain_model.py; Dec::decode_small
+// keeps its own chain). On 64 true window bits nearly every photo step runs all 16 links (the chain
+// leaves early only once 12 codes fill 63 bits). Measured, C5 decode: 1: 340.3-341.5 ms, 2:
+// 328.1-328.4, 4: 326.7-327.3; the latency-bound configs prefer 2 (one 4096 x 4096 stream -c -a -m:
+// 1202 / 1169 / 1177 ms; one 512 x 512 stream: 27.3 / 26.5 / 26.8), the flat alphabets leave at the
+// gate before any of it: 2 ships.
+#ifndef HC_DEC_CHAIN
+#define HC_DEC_CHAIN 2
+#endif
+static_assert(HC_DEC_CHAIN == 1 || HC_DEC_CHAIN == 2 || HC_DEC_CHAIN == 4, "chain stride");
 // HC_DEC_TOPUP 1: a batch step works on 64 true window bits -- the top 64 - nwin bits of the next
 // unread word are peeked into the window before the step (BitSource::peek), so a step takes codes
 // up to bit 62 whatever the window held; 0: the window's own 32..64 bits bound the step (tests/
@@ -2979,8 +2995,9 @@ struct Dec {
     // pads a short code, so a step takes as many codes as the window holds bits for; lane 63
     // is the root. The step:
     //  0. the depth of a code starting at every bit offset (the level-8 entries), the chain of
-    //     code starts S_j+1 = S_j + depth(S_j) on registers, and each lane's code index and
-    //     code start from the mask of start bits;
+    //     code starts S_j+1 = S_j + depth(S_j) on registers -- HC_DEC_CHAIN 2: every second start
+    //     from the depths of two codes, the others filled in lane-parallel -- and each lane's code
+    //     index and code start from the mask of start bits;
     //  1. every code's path positions get their increment tentatively, one LDS add (the root
     //     one per code, by lane 63), the words of the next positions having been read before;
     //  2. a level fails when that next word is below the position's word after the adds: the
@@ -3019,6 +3036,7 @@ struct Dec {
         // (measured and dropped on the 7 x 9 layout: the chain by pointer doubling, C5 decode
         // +0.8 %)
         uint32_t sv = lane == 0 ? 0u : 255u;
+#if HC_DEC_CHAIN == 1
         sv = writelane(sv, S, 1);
 #pragma unroll
         for (uint32_t j = 1; j < kPackMax; ++j) {
@@ -3026,6 +3044,43 @@ struct Dec {
             S += lane_read(dep, S);
             sv = writelane(sv, S, j + 1);
         }
+#else
+        // HC_DEC_CHAIN 2 / 4: the serial chain visits every second / fourth start only, on the depth
+        // map composed with itself (lane o: the bits of the two / four codes from bit o on; a code
+        // that ends past bit 63 counts 64 more, so nothing wraps into another offset's depth below
+        // bit 64), with the exit tests where the chain of single codes has them. The starts in
+        // between come lane-parallel afterwards: lane j of sv takes the start in the lane below it
+        // (stride 4: first the one two lanes below, from dep2, then the one below) plus that
+        // start's depth. Lanes whose source holds no start (255, or one past bit 63)
+        // get a value above 63 and keep their own through the min; the shift stays inside lanes
+        // 0..15, so lane 16 and up are never filled. A start at or past lim that the chain of
+        // single codes would have left at 255 after an exit is filled with a value above lim:
+        // nval, jmax, se and the start mask up to bit lim are the same (tests/fgk_chain_model.py).
+        constexpr uint32_t kCh = HC_DEC_CHAIN;
+        auto compose = [&](uint32_t d) __attribute__((always_inline)) {
+            const uint32_t nx = lane + d;
+            const uint32_t dn = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(nx * 4), (int)d);
+            return d + (nx < 64 ? dn : 64u);
+        };
+        const uint32_t dep2 = compose(dep);
+        const uint32_t depc = kCh == 4 ? compose(dep2) : dep2;
+        uint32_t E = lane_read(depc, 0);
+        sv = writelane(sv, E, kCh);
+#pragma unroll
+        for (uint32_t j = 2; j * kCh <= kPackMax; ++j) {
+            if ((j - 1) * kCh % 4 == 0 && E >= lim) break;
+            E += lane_read(depc, E);
+            sv = writelane(sv, E, j * kCh);
+        }
+        if constexpr (kCh == 4) {
+            const uint32_t pr = (uint32_t)__builtin_amdgcn_update_dpp(255, (int)sv, 0x112, 0x1, 0xF, false);  // row_shr:2, lanes 0..15
+            sv = min(sv, pr + (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pr * 4), (int)dep2));
+        }
+        {
+            const uint32_t pr = (uint32_t)__builtin_amdgcn_update_dpp(255, (int)sv, 0x111, 0x1, 0xF, false);  // row_shr:1, lanes 0..15
+            sv = min(sv, pr + (uint32_t)__builtin_amdgcn_ds_bpermute((int)(pr * 4), (int)dep));
+        }
+#endif
         // codes inside the window (S_j+1 <= lim; the starts grow, so these are the first nval)
         // and the block
         const uint32_t nval = (uint32_t)__builtin_popcountll(ballot(sv <= lim)) - 1;
