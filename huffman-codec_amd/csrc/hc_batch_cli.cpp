@@ -3,7 +3,7 @@
 // process, main.cpp:202-220). Each output is byte-identical to what `huffman-codec` (and the
 // reference) writes for that file alone.
 //
-//   huffman-codec-batch [-c | -d [-r OFFSET:LENGTH]] [-m] [-a [-w WIDTH]] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...
+//   huffman-codec-batch [-c | -d [-r OFFSET:LENGTH | -R X:Y:W:H]] [-m] [-a [-w WIDTH]] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...
 //   huffman-codec-batch -u OFFSET:PATCHFILE [-u ...] [-o OUTDIR] [-j THREADS] FILE...
 //   huffman-codec-batch -e TAILFILE [-o OUTDIR] [-j THREADS] FILE...
 //
@@ -24,6 +24,14 @@
 // name, through the same call: only the segments that hold the range are uploaded and
 // decoded. Every FILE must then be a container; another one reports "FILE: -r needs a segmented
 // container" and counts as HC_ERR_UNSUPPORTED (65). A range outside a container is HC_ERR_ARG (71).
+//
+// -R X:Y:W:H with -d writes the W x H rectangle at column X, row Y of the raw bytes read as rows of
+// PITCH bytes: the W * H bytes of its rows, back to back, under the same output name. PITCH is the
+// container's width when it is adaptive, otherwise -w (default 512). The rows are one read list of
+// hc_seg_decompress_ranges: each segment that holds rows of the rectangle is uploaded and decoded once.
+// Messages and exit codes follow -r: a FILE that is no container reports "FILE: -R needs a
+// segmented container" (65), a rectangle outside a container is HC_ERR_ARG (71). -R is given once,
+// with -d and without -r.
 //
 // -u OFFSET:PATCHFILE overwrites the raw bytes from OFFSET on with PATCHFILE's bytes in every FILE,
 // each a container, through hc_seg_update: only the segments that the new bytes touch are coded
@@ -63,6 +71,7 @@ const char *const kHelp =
     "  huffman-codec-batch [-cm] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch [-cm] -a [-w WIDTH] [-s BYTES [-k]] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch -d [-r OFFSET:LENGTH] [-o OUTDIR] [-j THREADS] FILE... | -h\n"
+    "  huffman-codec-batch -d -R X:Y:W:H [-w PITCH] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch -u OFFSET:PATCHFILE [-u ...] [-o OUTDIR] [-j THREADS] FILE...\n"
     "  huffman-codec-batch -e TAILFILE [-o OUTDIR] [-j THREADS] FILE...\n"
     "\n"
@@ -75,6 +84,8 @@ const char *const kHelp =
     "  -k     with -s: store a CRC-32 of every segment, verified by -d\n"
     "  -r     with -d: write only raw bytes [OFFSET, OFFSET + LENGTH) of every FILE,\n"
     "         each a segmented container\n"
+    "  -R     with -d: write only the W x H rectangle at column X, row Y of every FILE, each a\n"
+    "         segmented container; rows of PITCH bytes (an adaptive container's own width, else -w)\n"
     "  -u     overwrite the raw bytes from OFFSET on with PATCHFILE's bytes in every FILE,\n"
     "         each a segmented container; only the segments touched are coded again\n"
     "  -e     append TAILFILE's bytes to the raw bytes of every FILE, each a segmented\n"
@@ -102,15 +113,15 @@ std::string out_path(const std::string &in, bool compress, bool update, bool app
 }
 
 // run f(i) for i in [0, n) on `threads` host threads
-// "OFFSET:LENGTH", both decimal and nothing else
-bool parse_range(const char *arg, uint64_t &offset, uint64_t &length)
+// `count` decimal numbers with ':' between them and nothing else
+bool parse_numbers(const char *arg, uint64_t *v, int count)
 {
-    uint64_t v[2] = {0, 0};
     int k = 0;
     bool digits = false;
+    v[0] = 0;
     for (const char *p = arg; *p; ++p) {
-        if (*p == ':' && k == 0 && digits) {
-            k = 1;
+        if (*p == ':' && k + 1 < count && digits) {
+            v[++k] = 0;
             digits = false;
             continue;
         }
@@ -120,7 +131,14 @@ bool parse_range(const char *arg, uint64_t &offset, uint64_t &length)
         v[k] = v[k] * 10 + d;
         digits = true;
     }
-    if (k != 1 || !digits) return false;
+    return k == count - 1 && digits;
+}
+
+// "OFFSET:LENGTH", both decimal and nothing else
+bool parse_range(const char *arg, uint64_t &offset, uint64_t &length)
+{
+    uint64_t v[2];
+    if (!parse_numbers(arg, v, 2)) return false;
     offset = v[0];
     length = v[1];
     return true;
@@ -161,6 +179,8 @@ int main(int argc, char *argv[])
     bool compress = true, use_diff = false, use_adapt = false, segmented = false, check = false, ranged = false;
     bool update = false, coding_option = false;  // -u; any of -c -d -m -a -s -k -r, which -u goes with none of
     std::vector<std::pair<uint64_t, std::string>> patch_args;  // -u: (offset, patch file)
+    bool rect = false;      // -R
+    uint64_t rc_xywh[4] = {0, 0, 0, 0};
     bool append = false;    // -e
     std::string tail_path;  // -e: the file whose bytes are appended
     uint64_t seg_bytes = 0, r_offset = 0, r_length = 0;
@@ -168,7 +188,7 @@ int main(int argc, char *argv[])
     uint64_t width = 512;
     unsigned threads = 8;
     int opt;
-    while ((opt = getopt(argc, argv, ":cdmaw:s:kr:u:e:o:j:h")) != -1) {
+    while ((opt = getopt(argc, argv, ":cdmaw:s:kr:R:u:e:o:j:h")) != -1) {
         switch (opt) {
         case 'c': compress = true; break;
         case 'd': compress = false; break;
@@ -186,6 +206,13 @@ int main(int argc, char *argv[])
                 std::cerr << "ERROR: unrecognized option used\n";
                 return 2;
             }
+            break;
+        case 'R':
+            if (rect || !parse_numbers(optarg, rc_xywh, 4)) {  // one rectangle
+                std::cerr << "ERROR: unrecognized option used\n";
+                return 2;
+            }
+            rect = true;
             break;
         case 'u': {
             update = true;
@@ -212,7 +239,7 @@ int main(int argc, char *argv[])
         case ':': std::cerr << "ERROR: missing additional argument\n"; return 1;
         case '?': std::cerr << "ERROR: unrecognized option used\n"; return 2;
         }
-        if (opt == 'c' || opt == 'd' || opt == 'm' || opt == 'a' || opt == 's' || opt == 'k' || opt == 'r')
+        if (opt == 'c' || opt == 'd' || opt == 'm' || opt == 'a' || opt == 's' || opt == 'k' || opt == 'r' || opt == 'R')
             coding_option = true;
     }
     if ((update || append) && (coding_option || (update && append))) {  // a container describes itself: there is nothing to choose
@@ -224,6 +251,10 @@ int main(int argc, char *argv[])
         return 2;
     }
     if (ranged && compress) {  // a range is read, never written
+        std::cerr << "ERROR: unrecognized option used\n";
+        return 2;
+    }
+    if (rect && (compress || ranged)) {  // so is a rectangle, and it is a range list of its own
         std::cerr << "ERROR: unrecognized option used\n";
         return 2;
     }
@@ -301,6 +332,34 @@ int main(int argc, char *argv[])
             out[i].resize(cap ? cap : 1);  // (0: the call refuses the header or the tail's length, and says which)
             status[i] = hc_seg_append(in[i].data(), in[i].size(), tail.data(), tail.size(), out[i].data(), cap, &len,
                                       &bad_seg[i]);
+            out[i].resize(status[i] ? 0 : len);
+        }
+    } else if (rect) {
+        static const uint8_t kSegMagic[8] = {0x48, 0x43, 0x53, 0x45, 0x47, 0x31, 0x00, 0xFF};
+        const uint64_t x = rc_xywh[0], y = rc_xywh[1], w = rc_xywh[2], h = rc_xywh[3];
+        for (size_t i = 0; i < n; ++i) {
+            if (status[i]) continue;
+            if (in[i].size() < 8 || !std::equal(kSegMagic, kSegMagic + 8, in[i].begin())) {
+                status[i] = -4;  // reported below as HC_ERR_UNSUPPORTED
+                continue;
+            }
+            hc_seg_info_t info;
+            status[i] = hc_seg_info(in[i].data(), in[i].size(), &info);
+            if (status[i]) continue;
+            // one read per row (none for a rectangle without bytes, once its place is checked)
+            const uint64_t pitch = (info.flags & HC_FLAG_ADAPT) ? info.width : width;
+            const uint64_t rows = w ? h : 0;
+            std::vector<hc_seg_read_t> reads;
+            if (rows > UINT32_MAX) status[i] = HC_ERR_ARG;
+            else {
+                reads.resize(rows);
+                status[i] = hc_seg_rect_reads(info.raw_len, pitch, x, y, w, rows, reads.data());
+            }
+            if (status[i]) continue;
+            uint64_t len = 0;
+            out[i].resize(std::max<uint64_t>(w * rows, 1));
+            status[i] = hc_seg_decompress_ranges(in[i].data(), in[i].size(), reads.data(), (uint32_t)rows, out[i].data(),
+                                                 w * rows, &len, &bad_seg[i]);
             out[i].resize(status[i] ? 0 : len);
         }
     } else if (compress && segmented) {  // one container per file, all files in one call
@@ -451,8 +510,9 @@ int main(int argc, char *argv[])
             msgs[i] = files[i] + ": ERROR: given input file does not exist\n";
             return;
         }
-        if (status[i] == -1 || status[i] == -2 || status[i] == -3) {
-            msgs[i] = files[i] + (status[i] == -1 ? ": -r" : status[i] == -2 ? ": -u" : ": -e") + " needs a segmented container\n";
+        if (status[i] <= -1 && status[i] >= -4) {
+            msgs[i] = files[i] + (status[i] == -1 ? ": -r" : status[i] == -2 ? ": -u" : status[i] == -3 ? ": -e" : ": -R") +
+                      " needs a segmented container\n";
             status[i] = HC_ERR_UNSUPPORTED;
             return;
         }

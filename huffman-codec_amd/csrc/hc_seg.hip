@@ -22,6 +22,10 @@
 //           for the covered segments only; one that the range covers in part, or any at an offset
 //           that is no multiple of 4, decodes into a slot of the workspace, and a pack launch
 //           (hc_pipe.hip) moves its covered part to its place in out before seg_close
+//   reads   a list of byte ranges of one container (hc_seg_decompress_ranges*): the union of the
+//           segments they cover decodes once, every segment whole into one staging region of the
+//           workspace, and a pack launch moves every read's bytes to its own place in out (its own
+//           block comment below has the stages)
 //   update  a range write (hc_seg_update*): decode the segments that a patch covers in part, lay
 //           the patches over them, code the covered segments, and splice their new streams
 //           and the old container's other bytes into the new container (its own block comment
@@ -1107,6 +1111,261 @@ int decode_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, ui
 }
 
 // ---------------------------------------------------------------------------------------------
+// List read (hc_seg_decompress_ranges*): many byte ranges of one container, each covered segment
+// decoded once. The host plans the read list (hc_seg_index.h): the covered segments, in container
+// order, are the entries of one covered array, and covered entry c decodes whole to c full of a
+// staging region (only the container's last segment has another length, and it can only be the
+// last entry, so every entry starts 4-byte aligned and a read's bytes are one contiguous run).
+//
+//   rdesc    the read records, a chunk per launch as kernel arguments: the gather arrays
+//   rplan    covered entry c: its segment and the decoder's output, c full of the staging region
+//   ropen    one workgroup: header against the caller's copy, scan of the whole index (scan_index),
+//            the stream of every covered segment; the index's verdict, then the capacity's: either
+//            empties every decoder input and every gather range
+//   <decode launch over the covered entries, into staging; checked containers: their CRC-32>
+//   <pack launch: every read's bytes from staging to out + dst_off, at any byte alignment>
+//   rclose   one workgroup: the lowest failing covered entry, as its container index; the outputs
+// ---------------------------------------------------------------------------------------------
+using hc_seg_index::ReadPlan;
+using hc_seg_index::ReadRec;
+constexpr uint32_t kReadChunk = 80;  // read records per descriptor launch
+
+struct ReadWs {
+    ReadRec *recs;
+    uint64_t *g_src, *g_len, *g_dst;  // per read: g_len bytes from stage + g_src to out + g_dst
+    uint64_t *cov_seg;                // per covered entry: its segment
+    uint64_t *in_offs, *in_lens, *out_offs, *out_caps, *out_lens;  // per covered entry: the decoder's
+    int32_t *status;
+    uint32_t *crc;  // checked containers: the decoded segments' CRC-32
+    uint64_t *ctl;  // [0] the open kernel's verdict (0, HC_ERR_SEG_HEADER, HC_ERR_CAPACITY)
+    uint8_t *stage;
+    void *awork;
+    uint64_t awork_bytes, total;
+};
+ReadWs carve_reads(void *work, uint64_t P, uint64_t C, bool check, uint64_t stage_bytes, uint64_t awork_bytes)
+{
+    ReadWs w;
+    Carver cv(work);
+    w.recs = cv.arr<ReadRec>(P);
+    w.g_src = cv.take64(P);
+    w.g_len = cv.take64(P);
+    w.g_dst = cv.take64(P);
+    w.cov_seg = cv.take64(C);
+    w.in_offs = cv.take64(C);
+    w.in_lens = cv.take64(C);
+    w.out_offs = cv.take64(C);
+    w.out_caps = cv.take64(C);
+    w.out_lens = cv.take64(C);
+    w.status = cv.arr<int32_t>(C);
+    w.crc = cv.arr<uint32_t>(check ? C : 0);
+    w.ctl = cv.take64(2);
+    w.stage = cv.take(stage_bytes);
+    w.awork = cv.take(awork_bytes);
+    w.awork_bytes = awork_bytes;
+    w.total = cv.total();
+    return w;
+}
+static_assert(sizeof(ReadRec) == 48, "the work bound of hcodec.h counts this");
+
+// what the stages of a list read share
+struct ReadCall {
+    const uint8_t *in;
+    uint64_t in_len, skip;  // skip: what the covered segments' input offsets lose (a compact upload)
+    uint64_t out_cap, need;
+    HeaderWords h;  // the caller's host copy
+    uint64_t full, last;
+    uint64_t P, C;
+    uint32_t check;
+    ReadWs w;
+    uint64_t *out_len, *bad_segment;  // the call's three outputs
+    int32_t *status;
+};
+
+struct ReadChunk {
+    ReadRec rec[kReadChunk];
+    ReadRec *recs;
+    uint64_t *g_src, *g_len, *g_dst;
+    uint64_t base;
+    uint32_t count;
+};
+static_assert(sizeof(ReadChunk) <= 3968, "kernel arguments");
+
+__global__ __launch_bounds__(128) void seg_rdesc_kernel(ReadChunk c)
+{
+    if (threadIdx.x >= c.count) return;
+    const ReadRec r = c.rec[threadIdx.x];
+    const uint64_t g = c.base + threadIdx.x;
+    c.recs[g] = r;
+    c.g_src[g] = r.src;
+    c.g_len[g] = r.length;
+    c.g_dst[g] = r.dst_off;
+}
+
+// Covered entry c: its segment and its place in the staging region. The record to go by is the last
+// one whose e0 is <= c: e0 ascends over the list, that record's first segment lies in the same run
+// of covered segments as entry c (a record of a later run has a higher e0, and the record that
+// starts c's run has an e0 <= c), and inside a run k - c does not change.
+__global__ __launch_bounds__(256) void seg_rplan_kernel(ReadCall a)
+{
+    const uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.C) return;
+    const ReadWs &w = a.w;
+    uint64_t lo = 0, hi = a.P;  // recs[0].e0 is 0
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (w.recs[mid].e0 <= c) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t k = w.recs[lo].k0 + (c - w.recs[lo].e0);
+    w.cov_seg[c] = k;
+    w.in_offs[c] = 0;
+    w.in_lens[c] = 0;
+    w.out_offs[c] = c * a.full;
+    w.out_caps[c] = k == a.h.n - 1 ? a.last : a.full;
+    w.out_lens[c] = 0;
+    w.status[c] = HC_ERR_DEVICE;  // overwritten by the decode launch
+}
+
+// scan_index for a list read: the stream of every covered segment (found in cov_seg, which
+// ascends, by search). A failed index, or an output too small for the reads, empties every decoder
+// input, which the coders answer with HC_ERR_HEADER before they touch anything (and which the CRC
+// gate then passes over), and every gather range: nothing of the container is read, no byte of out
+// is written.
+__global__ __launch_bounds__(kScan) void seg_ropen_kernel(ReadCall a)
+{
+    const uint32_t tid = threadIdx.x;
+    const ReadWs &w = a.w;
+    const bool bad = scan_index(a.in, a.h, a.in_len, a.check != 0, [&](uint64_t k, uint64_t off, uint64_t len) {
+        uint64_t lo = 0, hi = a.C;  // the first entry whose segment is >= k
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (w.cov_seg[mid] < k) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < a.C && w.cov_seg[lo] == k) {
+            w.in_offs[lo] = off - a.skip;
+            w.in_lens[lo] = len;
+        }
+    });
+    const int32_t st = bad ? HC_ERR_SEG_HEADER : (a.out_cap < a.need ? HC_ERR_CAPACITY : 0);
+    if (tid == 0) w.ctl[0] = (uint64_t)st;
+    if (st == 0) return;
+    for (uint64_t c = tid; c < a.C; c += kScan) w.in_lens[c] = 0;
+    for (uint64_t i = tid; i < a.P; i += kScan) w.g_len[i] = 0;
+}
+
+// the verdict over the covered entries; bad_segment is the container's index
+__global__ __launch_bounds__(kScan) void seg_rclose_kernel(ReadCall a)
+{
+    __shared__ unsigned long long s_bad;
+    const uint32_t tid = threadIdx.x;
+    const ReadWs &w = a.w;
+    // checked containers: the decoded bytes' crc against the index's
+    const uint32_t *want_crc = a.check ? reinterpret_cast<const uint32_t *>(a.in + 48 + 8 * a.h.n) : nullptr;
+    if (tid == 0) s_bad = kNoSeg;
+    __syncthreads();
+    const int32_t top = (int32_t)w.ctl[0];
+    if (top == 0)
+        lowest_failing(a.C, &s_bad, [&](uint64_t c) {
+            return w.status[c] != 0 || w.out_lens[c] != w.out_caps[c] || (want_crc && w.crc[c] != want_crc[w.cov_seg[c]]);
+        });
+    __syncthreads();
+    if (tid != 0) return;
+    const uint64_t bad = s_bad;
+    int32_t st = top;
+    uint64_t len = top == HC_ERR_CAPACITY ? a.need : 0;
+    if (top == 0) {
+        if (bad != kNoSeg) st = decoded_verdict(w.status[bad], w.out_lens[bad], w.out_caps[bad]);
+        else len = a.need;
+    }
+    *a.status = st;
+    *a.out_len = len;
+    if (a.bad_segment) *a.bad_segment = bad == kNoSeg ? kNoSeg : w.cov_seg[bad];
+}
+
+// the sizes of a list read whose info passed info_ok and whose reads passed reads_ok; enc_total: a
+// bound of the covered segments' encoded bytes (the adaptive decoder's workspace goes by it)
+struct ReadSizes {
+    Cuts c;
+    ReadPlan u;
+    uint64_t need, awork_bytes;
+    bool adapt, check;
+};
+ReadSizes read_sizes(const hc_seg_info_t &info, uint64_t in_len, const hc_seg_read_t *reads, uint32_t n_reads,
+                     uint64_t enc_total, ReadRec *recs)
+{
+    ReadSizes s;
+    (void)info_ok(info, in_len, s.c);
+    (void)hc_seg_index::reads_ok(info.raw_len, reads, n_reads, &s.need);
+    s.adapt = (info.flags & HC_FLAG_ADAPT) != 0;
+    s.check = checked(info.flags);
+    s.u = hc_seg_index::reads_plan(s.c, info.raw_len, reads, n_reads, recs);
+    s.awork_bytes = (s.adapt && s.u.covered && s.u.covered <= kMaxSegs)
+                        ? hc::adapt_decode_work_bound(enc_total, s.u.cov_raw, (uint32_t)s.u.covered)
+                        : 0;
+    return s;
+}
+ReadWs reads_ws(void *work, const ReadSizes &s, uint32_t n_reads)
+{
+    return carve_reads(work, n_reads, s.u.covered, s.check, s.u.cov_raw, s.awork_bytes);
+}
+
+// hc_seg_decompress_ranges_dev; the host call passes its compact upload's skip and span
+int reads_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info, const hc_seg_read_t *reads,
+              uint32_t n_reads, uint8_t *out, uint64_t out_cap, uint64_t *out_len, int32_t *status, uint64_t *bad_segment,
+              void *work, uint64_t work_bytes, void *stream, uint64_t skip, uint64_t enc_total)
+{
+    if (!in || !info || !out || !out_len || !status || !work || (!reads && n_reads)) return HC_ERR_ARG;
+    if (!aligned16(in) || !aligned16(out) || !aligned16(work)) return HC_ERR_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Cuts c;
+    if (!info_ok(*info, in_len, c)) {
+        seg_reject_kernel<<<1, 1, 0, st>>>(out_len, status, bad_segment);
+        HC_CK(hipGetLastError());
+        return HC_OK;
+    }
+    if (!hc_seg_index::reads_ok(info->raw_len, reads, n_reads, nullptr)) return HC_ERR_ARG;
+    std::vector<ReadRec> recs(n_reads);
+    const ReadSizes s = read_sizes(*info, in_len, reads, n_reads, enc_total, recs.data());
+    if (s.u.covered > kMaxSegs) return HC_ERR_ARG;
+    const ReadWs w = reads_ws(work, s, n_reads);
+    if (work_bytes < w.total) return HC_ERR_ARG;
+    const uint64_t P = n_reads, C = s.u.covered;
+    const ReadCall a{in, in_len, skip, out_cap, s.need,
+                     HeaderWords{get64(kMagic), info->flags & 0xFFFFu, info->raw_len, info->seg_bytes, info->width, c.n},
+                     c.full, c.last, P, C, s.check ? 1u : 0u, w, out_len, bad_segment, status};
+
+    for (uint64_t base = 0; base < P; base += kReadChunk) {
+        ReadChunk ch;
+        ch.count = (uint32_t)(P - base < kReadChunk ? P - base : kReadChunk);
+        memcpy(ch.rec, recs.data() + base, sizeof(ReadRec) * ch.count);
+        ch.recs = w.recs;
+        ch.g_src = w.g_src;
+        ch.g_len = w.g_len;
+        ch.g_dst = w.g_dst;
+        ch.base = base;
+        seg_rdesc_kernel<<<1, 128, 0, st>>>(ch);
+    }
+    if (C) seg_rplan_kernel<<<(uint32_t)((C + 255) / 256), 256, 0, st>>>(a);
+    seg_ropen_kernel<<<1, kScan, 0, st>>>(a);
+    HC_CK(hipGetLastError());
+    if (C) {
+        Batch b{in, w.in_offs, w.in_lens, (uint32_t)C, w.stage, w.out_offs, w.out_caps, w.out_lens, w.status, 0};
+        if (s.adapt) HC_CK(hc::adapt_decode_batch(b, w.awork, w.awork_bytes, st));
+        else HC_CK(hc::launch_decode(b, hc::DST_RAW, st));
+        // every covered segment decodes whole, so its checksum is verifiable; the gate keeps the launch
+        // away from one that did not decode cleanly to its cut's length
+        if (s.check)
+            HC_CK(hc::launch_crc32(w.stage, w.out_offs, w.out_caps, C, w.crc, hc::CrcGate{w.status, w.out_lens}, st));
+        // every read's bytes to its place in out (empty copies when the open kernel's verdict is set)
+        HC_CK(hc::launch_pack(w.stage, w.g_src, w.g_len, n_reads, out, w.g_dst, st));
+    }
+    seg_rclose_kernel<<<1, kScan, 0, st>>>(a);
+    HC_CK(hipGetLastError());
+    return HC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Range write (hc_seg_update*): the container with some raw byte ranges overwritten, without
 // recoding the rest. The host plans the patch list (hc_seg_index.h): the covered segments, in
 // container order, are the entries of one covered array, and those that a patch covers only in part
@@ -2042,6 +2301,94 @@ int hc_seg_decompress_range(const uint8_t *in, uint64_t in_len, uint64_t offset,
     if (status) return status;
     if (*out_len) HC_CK(hipMemcpy(out, dout.p, *out_len, hipMemcpyDeviceToHost));
     return HC_OK;
+}
+
+int hc_seg_reads_segments(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_read_t *reads, uint32_t n_reads,
+                          uint64_t *n_covered, uint64_t *need)
+{
+    if (!info || !n_covered || !need) return HC_ERR_ARG;
+    Cuts c;
+    uint64_t top = 0;
+    if (!info_ok(*info, in_len, c) || !hc_seg_index::reads_ok(info->raw_len, reads, n_reads, &top)) return HC_ERR_ARG;
+    *n_covered = hc_seg_index::reads_plan(c, info->raw_len, reads, n_reads, nullptr).covered;
+    *need = top;
+    return HC_OK;
+}
+
+uint64_t hc_seg_decompress_ranges_work_bound(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_read_t *reads,
+                                             uint32_t n_reads)
+{
+    if (!info) return 0;
+    Cuts c;
+    if (!info_ok(*info, in_len, c)) return 16;  // rejected without a workspace
+    if (!hc_seg_index::reads_ok(info->raw_len, reads, n_reads, nullptr)) return 0;
+    const ReadSizes s = read_sizes(*info, in_len, reads, n_reads, in_len, nullptr);
+    if (s.u.covered > kMaxSegs) return 0;
+    return reads_ws(nullptr, s, n_reads).total;
+}
+
+int hc_seg_decompress_ranges_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info,
+                                 const hc_seg_read_t *reads, uint32_t n_reads, uint8_t *out, uint64_t out_cap,
+                                 uint64_t *out_len, int32_t *status, uint64_t *bad_segment, void *work,
+                                 uint64_t work_bytes, void *stream)
+{
+    return reads_dev(in, in_len, info, reads, n_reads, out, out_cap, out_len, status, bad_segment, work, work_bytes, stream,
+                     0, in_len);
+}
+
+int hc_seg_decompress_ranges(const uint8_t *in, uint64_t in_len, const hc_seg_read_t *reads, uint32_t n_reads,
+                             uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment)
+{
+    if ((!in && in_len) || !out_len || (!out && out_cap) || (!reads && n_reads)) return HC_ERR_ARG;
+    hc_seg_info_t info;
+    if (hc_seg_info(in, in_len, &info) != HC_OK) return fail(HC_ERR_SEG_HEADER, 0, out_len, bad_segment);
+    if (!hc_seg_index::reads_ok(info.raw_len, reads, n_reads, nullptr)) return HC_ERR_ARG;
+    ReadSizes s = read_sizes(info, in_len, reads, n_reads, in_len, nullptr);
+    if (s.u.covered > kMaxSegs) return HC_ERR_ARG;
+    // the index on the host: the verdict without a device, and the encoded bytes [s0, s1) from the
+    // first covered segment's stream to the last covered one's
+    uint64_t s0 = 0, s1 = 0;
+    const uint64_t idx = align16(index_end(s.c.n, s.check));
+    const Cover span_cv = s.u.covered ? Cover{s.u.k_lo, s.u.k_hi - s.u.k_lo + 1} : Cover{0, 0};
+    if (hc_seg_index::index_scan(in, in_len, s.c.n, s.check, span_cv, &s0, &s1) != HC_OK)
+        return fail(HC_ERR_SEG_HEADER, 0, out_len, bad_segment);
+    if (!hc_device_ok()) return fail(HC_ERR_DEVICE, 0, out_len, bad_segment);
+    if (out_cap < s.need) return fail(HC_ERR_CAPACITY, s.need, out_len, bad_segment);
+    (void)fail(HC_OK, 0, out_len, bad_segment);  // (what a HIP error below leaves behind)
+    // the compact upload: header and index [0, idx), then the span; in_len stays the container's
+    const uint64_t span = s1 - s0;
+    s = read_sizes(info, in_len, reads, n_reads, span, nullptr);  // the adaptive workspace by the span's own length
+    const uint64_t wb = reads_ws(nullptr, s, n_reads).total;
+    hipStream_t st = nullptr;
+    DevBuf din, dout, work, meta;
+    HC_CK(din.alloc(idx + span + 16));
+    HC_CK(dout.alloc(s.need + 16));
+    HC_CK(work.alloc(wb));
+    HC_CK(meta.alloc(32));
+    HC_CK(hipMemcpyAsync(din.p, in, idx, hipMemcpyHostToDevice, st));
+    if (span) HC_CK(hipMemcpyAsync(din.as<uint8_t>() + idx, in + s0, span, hipMemcpyHostToDevice, st));
+    uint64_t *m = meta.as<uint64_t>();
+    const int rc = reads_dev(din.as<uint8_t>(), in_len, &info, reads, n_reads, dout.as<uint8_t>(), s.need, m,
+                             reinterpret_cast<int32_t *>(m + 1), m + 2, work.p, wb, st, s0 - idx, span);
+    if (rc) return rc;
+    const int status = read_verdict(meta, st, out_len, bad_segment);
+    if (status) return status;
+    // the destination bytes [0, need) come down, and go into out read by read: no byte outside the
+    // destination ranges is written here either
+    if (s.need) {
+        std::vector<uint8_t> down(s.need);
+        HC_CK(hipMemcpy(down.data(), dout.p, s.need, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n_reads; ++i)
+            if (reads[i].length) memcpy(out + reads[i].dst_off, down.data() + reads[i].dst_off, reads[i].length);
+    }
+    return HC_OK;
+}
+
+int hc_seg_rect_reads(uint64_t raw_len, uint64_t pitch, uint64_t x, uint64_t y, uint64_t w, uint64_t h,
+                      hc_seg_read_t *reads)
+{
+    if (!reads && h) return HC_ERR_ARG;
+    return hc_seg_index::rect_reads(raw_len, pitch, x, y, w, h, reads) ? HC_OK : HC_ERR_ARG;
 }
 
 int hc_seg_update_segments(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_patch_t *patches,

@@ -229,6 +229,106 @@ inline UpdPlan update_plan(const Cuts &c, uint64_t raw, const hc_seg_patch_t *p,
 }
 
 // ---------------------------------------------------------------------------------------------
+// List read (hc_seg_decompress_ranges*): the host's plan of a read list. The covered segments of
+// a call, in container order, are the entries 0 .. covered - 1 of its covered array, each once
+// however many reads name it; covered entry c decodes to c full of a staging region. A read's
+// covered segments are consecutive entries, and only segment n - 1 (the highest entry when it is
+// covered) has another length than full, so a read's bytes are one contiguous run of that region.
+// ---------------------------------------------------------------------------------------------
+// The read list's rules: every read inside raw_len, sorted by offset (source ranges may overlap
+// or repeat), no dst_off + length that wraps. n_reads > 0 needs the list. *need (or null): the
+// highest dst_off + length of the reads that are not empty, 0 when there is none.
+inline bool reads_ok(uint64_t raw_len, const hc_seg_read_t *r, uint32_t n_reads, uint64_t *need)
+{
+    if (n_reads && !r) return false;
+    uint64_t prev = 0, top = 0;
+    for (uint32_t i = 0; i < n_reads; ++i) {
+        if (!range_ok(raw_len, r[i].offset, r[i].length)) return false;
+        if (r[i].offset < prev) return false;  // unsorted
+        prev = r[i].offset;
+        if (r[i].dst_off + r[i].length < r[i].dst_off) return false;
+        if (r[i].length && r[i].dst_off + r[i].length > top) top = r[i].dst_off + r[i].length;
+    }
+    if (need) *need = top;
+    return true;
+}
+
+// One read as the device stages see it. It covers the segments k0 .. k0 + cnt - 1, the covered
+// entries e0 .. e0 + cnt - 1, and its `length` bytes lie at `src` of the staging region, e0 full +
+// (offset - k0 full); they go to out + dst_off. An empty read covers nothing (cnt 0) and carries
+// the k0 and e0 of the read before it (0 and 0 when it is the first), so that e0 ascends over the
+// whole list and k0 - e0 is what it is for every entry of the run of segments the list has reached.
+struct ReadRec {
+    uint64_t k0, cnt, e0;
+    uint64_t src, length, dst_off;
+};
+struct ReadPlan {
+    uint64_t covered, cov_raw;  // the covered segments, their raw bytes
+    uint64_t k_lo, k_hi;        // the lowest and the highest covered segment (covered > 0)
+};
+// Walks a read list that passed reads_ok once. recs (or null): n_reads records. The offsets
+// ascend, so the first covered segments do, and every segment below `next` is counted: a read that
+// starts below it starts inside the last run of covered segments, next - a entries from its end.
+inline ReadPlan reads_plan(const Cuts &c, uint64_t raw, const hc_seg_read_t *r, uint32_t n_reads, ReadRec *recs)
+{
+    ReadPlan u{0, 0, 0, 0};
+    uint64_t next = 0, k0 = 0, e0 = 0;
+    for (uint32_t i = 0; i < n_reads; ++i) {
+        const Cover cv = range_cover(c, r[i].offset, r[i].length);
+        ReadRec rec{k0, 0, e0, 0, r[i].length, r[i].dst_off};
+        if (cv.count) {
+            const uint64_t a = cv.k0, b = cv.k0 + cv.count - 1;
+            if (u.covered == 0) u.k_lo = a;
+            k0 = a;
+            e0 = a >= next ? u.covered : u.covered - (next - a);
+            rec.k0 = k0;
+            rec.cnt = cv.count;
+            rec.e0 = e0;
+            rec.src = e0 * c.full + (r[i].offset - a * c.full);
+            if (b >= next) {  // the segments max(a, next) .. b are new
+                const uint64_t first = a > next ? a : next, cnt = b - first + 1;
+                u.covered += cnt;
+                u.cov_raw += (cnt - 1) * c.full + (b == c.n - 1 ? raw - b * c.full : c.full);
+                u.k_hi = b;
+                next = b + 1;
+            }
+        }
+        if (recs) recs[i] = rec;
+    }
+    return u;
+}
+// hc_seg_decompress_ranges_work_bound without the adaptive workspace (P reads, C covered segments
+// of W raw bytes): the records, the three gather arrays, the covered entries' segment and five
+// decoder arrays, the status (and crc) words, 16 of control words and the staging region.
+inline uint64_t reads_work_base(uint64_t P, uint64_t C, uint64_t W, bool check)
+{
+    if (W > ~0ull - 15) return ~0ull;
+    const uint64_t t = align16(sizeof(ReadRec) * P) + 3 * align16(8 * P) + 6 * align16(8 * C) + align16(4 * C) +
+                       (check ? align16(4 * C) : 0) + 16;
+    return sat_add(t, align16(W));
+}
+// hc_seg_rect_reads after its null check: row r of the rectangle is bytes [(y + r) pitch + x, + w).
+// rect_ok: the argument rules alone.
+inline bool rect_ok(uint64_t raw_len, uint64_t pitch, uint64_t x, uint64_t y, uint64_t w, uint64_t h)
+{
+    if (pitch == 0 || x + w < x || x + w > pitch) return false;
+    if (h) {
+        // the last row's end, (y + h - 1) pitch + x + w, and the last destination's, h w, without a wrap
+        const uint64_t row = y + (h - 1);
+        if (row < y || row > ~0ull / pitch || row * pitch > ~0ull - (x + w) || (w && h > ~0ull / w)) return false;
+        if (w && row * pitch + x + w > raw_len) return false;
+    }
+    return true;
+}
+inline bool rect_reads(uint64_t raw_len, uint64_t pitch, uint64_t x, uint64_t y, uint64_t w, uint64_t h,
+                       hc_seg_read_t *reads)
+{
+    if (!rect_ok(raw_len, pitch, x, y, w, h)) return false;
+    for (uint64_t r = 0; r < h; ++r) reads[r] = hc_seg_read_t{(y + r) * pitch + x, w, r * w};
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Append (hc_seg_append*): the host's plan of raw bytes added behind a container. The cuts of
 // raw + add agree with the old ones on every segment below the old last one, and on that one too
 // when it already had the shape of a cut that is not the last. Segments 0 .. K - 1 are kept; the

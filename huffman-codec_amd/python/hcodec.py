@@ -73,6 +73,11 @@ class SegPatch(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("src_off", ctypes.c_uint64)]
 
 
+class SegRead(ctypes.Structure):
+    """hc_seg_read_t: raw bytes [offset, offset + length) go to out[dst_off .. dst_off + length)"""
+    _fields_ = [("offset", ctypes.c_uint64), ("length", ctypes.c_uint64), ("dst_off", ctypes.c_uint64)]
+
+
 SYNTH = {"noise": 0, "grad": 1, "photo": 2}
 
 _libs = {}           # path -> loaded library
@@ -181,6 +186,16 @@ def _load(path):
                                     vp, u64, vp]
     L.hc_seg_update.argtypes = [u8p, u64, pp, ctypes.c_uint32, u8p, u64, u8p, u64, ctypes.POINTER(u64),
                                 ctypes.POINTER(u64)]
+    rp = ctypes.POINTER(SegRead)
+    L.hc_seg_reads_segments.argtypes = [ctypes.POINTER(SegInfo), u64, rp, ctypes.c_uint32, ctypes.POINTER(u64),
+                                        ctypes.POINTER(u64)]
+    L.hc_seg_decompress_ranges_work_bound.argtypes = [ctypes.POINTER(SegInfo), u64, rp, ctypes.c_uint32]
+    L.hc_seg_decompress_ranges_work_bound.restype = u64
+    L.hc_seg_decompress_ranges_dev.argtypes = [vp, u64, ctypes.POINTER(SegInfo), rp, ctypes.c_uint32, vp, u64, vp, vp, vp,
+                                               vp, u64, vp]
+    L.hc_seg_decompress_ranges.argtypes = [u8p, u64, rp, ctypes.c_uint32, u8p, u64, ctypes.POINTER(u64),
+                                           ctypes.POINTER(u64)]
+    L.hc_seg_rect_reads.argtypes = [u64, u64, u64, u64, u64, u64, rp]
     L.hc_seg_append_plan.argtypes = [ctypes.POINTER(SegInfo), u64, u64, ctypes.POINTER(SegInfo), ctypes.POINTER(u64),
                                      ctypes.POINTER(u64)]
     for f in (L.hc_seg_append_bound, L.hc_seg_append_work_bound):
@@ -641,6 +656,89 @@ def seg_update_dev(inp, patches, patch_data, out, out_len, status, bad_segment=N
                                  _dp(work), work.numel(), _stream_handle(stream))
     if rc:
         raise HCodecError(f"hc_seg_update_dev failed: {rc}")
+    return work
+
+
+def seg_reads(reads):
+    """a ctypes array of SegRead from (offset, length, dst_off) triples (None when there are none)"""
+    reads = list(reads)
+    if not reads:
+        return None
+    return (SegRead * len(reads))(*[SegRead(o, m, d) for o, m, d in reads])
+
+
+def seg_reads_segments(info, in_len, reads):
+    """hc_seg_reads_segments (host only, no device): (status, covered segments, need) of a list of
+    (offset, length, dst_off) reads; need is the output bytes the list reaches"""
+    cov = ctypes.c_uint64(0)
+    need = ctypes.c_uint64(0)
+    st = lib().hc_seg_reads_segments(ctypes.byref(info) if info is not None else None, in_len, seg_reads(reads),
+                                     len(reads), ctypes.byref(cov), ctypes.byref(need))
+    return st, cov.value, need.value
+
+
+def seg_decompress_ranges_work_bound(info, in_len, reads):
+    """hc_seg_decompress_ranges_work_bound: the device call's workspace (0: refused; 16: an info that fails)"""
+    return int(lib().hc_seg_decompress_ranges_work_bound(ctypes.byref(info) if info is not None else None, in_len,
+                                                         seg_reads(reads), len(reads)))
+
+
+def seg_rect_reads(raw_len, pitch, x, y, w, h):
+    """hc_seg_rect_reads (host only): (status, the (offset, length, dst_off) reads of the rows of the
+    w x h rectangle at column x, row y of raw bytes read as rows of `pitch` bytes)"""
+    arr = (SegRead * max(int(h), 1))() if h < 2**32 else None
+    st = lib().hc_seg_rect_reads(raw_len, pitch, x, y, w, h, arr)
+    return st, ([(r.offset, r.length, r.dst_off) for r in arr[:h]] if st == 0 else [])
+
+
+def seg_decompress_ranges(data, reads, full=False, cap=None, fill=0):
+    """hc_seg_decompress_ranges: (status, out[:need]) with the (offset, length, dst_off) reads of the
+    container's raw bytes at their destinations and every other byte `fill`; full: (status, bytes,
+    out_len, bad_segment). cap: the output capacity (default: need). The reads must be sorted by
+    offset; each covered segment is uploaded and decoded once."""
+    b, p = _buf(data)
+    reads = list(reads)
+    arr = seg_reads(reads)
+    if cap is None:
+        st, info = seg_info(b)
+        cap = seg_reads_segments(info, len(b), reads)[2] if st == 0 else 0
+    out = ctypes.create_string_buffer(bytes([fill]) * max(int(cap), 1), max(int(cap), 1))
+    n = ctypes.c_uint64(0)
+    bad = ctypes.c_uint64(NO_SEGMENT)
+    st = lib().hc_seg_decompress_ranges(p, len(b), arr, len(reads), ctypes.cast(out, ctypes.c_void_p), cap,
+                                        ctypes.byref(n), ctypes.byref(bad))
+    got = out.raw[:n.value] if st == 0 else b""
+    return (st, got, n.value, bad.value) if full else (st, got)
+
+
+def seg_decompress_ranges_dev(inp, reads, out, out_len, status, bad_segment=None, info=None, stream=None, work=None,
+                              in_len=None, out_cap=None):
+    """hc_seg_decompress_ranges_dev on CUDA tensors: the (offset, length, dst_off) reads of the
+    container in inp[:in_len] into `out` (capacity out_cap, default all of it). info as for
+    seg_decompress_dev. A read list that fails its rules raises. Returns the workspace."""
+    _check_seg(inp, out, out_len, status, bad_segment)
+    n = inp.numel() if in_len is None else int(in_len)
+    if n > inp.numel():
+        raise ValueError(f"in_len {n} exceeds the {inp.numel()}-byte input tensor")
+    cap = out.numel() if out_cap is None else int(out_cap)
+    if cap > out.numel():
+        raise ValueError(f"out_cap {cap} exceeds the {out.numel()}-byte output tensor")
+    if info is None:
+        head, p = _buf(inp[:min(n, 48)].cpu().numpy().tobytes())
+        info = SegInfo()  # stays all zero when the header does not parse: the call rejects it
+        lib().hc_seg_info(p, n, ctypes.byref(info))
+    reads = list(reads)
+    arr = seg_reads(reads)
+    need = int(lib().hc_seg_decompress_ranges_work_bound(ctypes.byref(info), n, arr, len(reads)))
+    if work is None:
+        work = _work(need, inp.device)
+    _check_work(work, inp.device, need)
+    rc = lib().hc_seg_decompress_ranges_dev(_dp(inp), n, ctypes.byref(info), arr, len(reads), _dp(out), cap,
+                                            _dp(out_len), _dp(status),
+                                            ctypes.c_void_p(None) if bad_segment is None else _dp(bad_segment),
+                                            _dp(work), work.numel(), _stream_handle(stream))
+    if rc:
+        raise HCodecError(f"hc_seg_decompress_ranges_dev failed: {rc}")
     return work
 
 

@@ -474,6 +474,105 @@ int hc_seg_update(const uint8_t *in, uint64_t in_len, const hc_seg_patch_t *patc
                   uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment);
 
 /* ---------------------------------------------------------------------------------------
+ * List read: many raw byte ranges of one container in one call, each covered segment decoded
+ * once. The read mirror of the range write: a tile of an image is one read per row, and the rows
+ * that share a segment share its one decode, its one CRC-32 and its one place in the workspace.
+ *
+ * Reads. A call takes a list: read i copies raw bytes [offset, offset + length) of the container to
+ * out[dst_off .. dst_off + length). `reads` is HOST memory, read before the call returns and never
+ * after (the list travels as kernel arguments, in chunks, so a call can be captured in a graph).
+ * Every read must lie inside raw_len (offset <= raw_len and length <= raw_len - offset); the reads
+ * must be sorted by offset (reads[i+1].offset >= reads[i].offset); no dst_off + length may wrap.
+ * Anything else is HC_ERR_ARG, decided on the host. Source ranges MAY overlap or repeat: this is a
+ * read. A read of length 0 is valid at any offset inside raw_len and touches nothing; n_reads == 0 is
+ * valid. Destination ranges must not overlap one another: that is the caller's duty, as in
+ * hc_pack_batch, and it is not checked. They may come in any order, at any byte alignment, with gaps
+ * between them. need is the highest dst_off + length over the reads of length > 0, 0 when there is
+ * none.
+ *
+ * Covered segments. A read of length > 0 covers the segments that hc_seg_range_segments names for its
+ * range (clamp to n - 1 included); a call covers the union over its reads, C segments. Each covered
+ * segment is decoded whole exactly once, however many reads name it, and in a checked container
+ * verified against the index's CRC-32 once. A damaged segment that no read covers is not noticed, as
+ * in every ranged read.
+ *
+ * Status, in this order (the range decoder's):
+ *   1  HC_ERR_ARG         null pointers (device call: in, out or work not 16-byte aligned)
+ *                                                                            *out_len, *bad_segment not set
+ *   2  HC_ERR_SEG_HEADER  the header fails                                   0, UINT64_MAX
+ *   3  HC_ERR_ARG         the list fails its rules (device call: work_bytes below the bound; more
+ *                         than 2^31 - 1 covered segments)                    not set
+ *   4  HC_ERR_SEG_HEADER  the index fails: all n entries are scanned once and must tile the container
+ *                         exactly, whatever the list, the empty one included   0, UINT64_MAX
+ *   5  HC_ERR_DEVICE      host call without a device                         0, UINT64_MAX
+ *   6  HC_ERR_CAPACITY    out_cap < need                                     need, UINT64_MAX
+ *   7  the status of the lowest failing COVERED segment in container order, by hc_seg_decompress's
+ *      mapping (the coder's own status; another length than the cut: HC_ERR_SEG_SIZE; in a checked
+ *      container the right length with another CRC-32: HC_ERR_SEG_CHECK)     0, its container index
+ *   8  HC_OK                                                                 need, UINT64_MAX
+ *
+ * Writes. No byte outside the union of the destination ranges is written, whatever the status; on a
+ * non-zero status the contents of those ranges are unspecified. A list of the one read (o, m, 0)
+ * gives exactly what hc_seg_decompress_range* gives for (o, m) with the same out_cap: status, bytes,
+ * *out_len and *bad_segment (the work bound and the launches may differ).
+ * ------------------------------------------------------------------------------------- */
+typedef struct hc_seg_read_t {
+    uint64_t offset, length; /* raw bytes [offset, offset + length) of the container ...   */
+    uint64_t dst_off;        /* ... go to out[dst_off .. dst_off + length)                  */
+} hc_seg_read_t;
+
+/* Host only, no device. *n_covered = C, the segments the call decodes; *need as above. HC_OK, or
+ * HC_ERR_ARG (a null pointer, an info that fails hc_seg_info's rules for in_len, a list that fails
+ * the rules above). */
+int hc_seg_reads_segments(const hc_seg_info_t *info, uint64_t in_len, const hc_seg_read_t *reads,
+                          uint32_t n_reads, uint64_t *n_covered, uint64_t *need);
+/* The device call's workspace. With P = n_reads, C the covered segments, W their raw bytes and
+ * a16(x) = x rounded up to a multiple of 16:
+ *   a16(48 P) + 3 a16(8 P) + 6 a16(8 C) + a16(4 C) + 16 [+ a16(4 C) checked] + a16(W)
+ *   [+ a16(hc_adapt_decompress_work_bound(in_len, W, C)) adaptive, C > 0]
+ * It grows with the reads and with the segments they cover, never with n or with how often a
+ * segment is named. 0 for a null info, a list that fails the rules or more than 2^31 - 1 covered
+ * segments; 16 for an info that fails hc_seg_info's rules (as hc_seg_decompress_work_bound). */
+uint64_t hc_seg_decompress_ranges_work_bound(const hc_seg_info_t *info, uint64_t in_len,
+                                             const hc_seg_read_t *reads, uint32_t n_reads);
+
+/* Device buffers, asynchronous on `stream`, under the rules of hc_seg_update_dev: in, out and work
+ * 16-byte aligned; out_len, status and bad_segment (may be NULL) DEVICE pointers; no device
+ * allocation, no host synchronisation, no host read of device memory, every byte of scratch from
+ * `work`; capturable in a graph. `in` holds the whole container (of which the header, the index and
+ * the covered segments are read). Rows 1 and 3 are the return value; an info that fails
+ * hc_seg_info's rules gives HC_ERR_SEG_HEADER as the device status with return value HC_OK;
+ * everything else is the device status.
+ *
+ * Covered segment c (in container order) decodes whole to c full of a staging region in `work`, all
+ * of them in one launch. A read's covered segments are consecutive there and only segment n - 1,
+ * the last entry when it is covered, has another length than full, so read i's bytes are one run of
+ * that region, and one pack launch copies every run to out + dst_off at any byte alignment. The
+ * index is scanned by one workgroup, once. */
+int hc_seg_decompress_ranges_dev(const uint8_t *in, uint64_t in_len, const hc_seg_info_t *info,
+                                 const hc_seg_read_t *reads, uint32_t n_reads, uint8_t *out, uint64_t out_cap,
+                                 uint64_t *out_len, int32_t *status, uint64_t *bad_segment,
+                                 void *work, uint64_t work_bytes, void *stream);
+
+/* Host buffers, synchronous. The header, the list and the index are checked on the host (rows 2 - 4
+ * need no device); the header, the index and the encoded bytes from the first covered segment's
+ * stream to the last covered one's are uploaded, never the whole container when the reads cover part
+ * of it; the device call runs on the cached scratch of the single calls; the destination bytes
+ * [0, need) come down and are copied into out read by read, so no byte outside the destination
+ * ranges is written on the host either. bad_segment may be NULL. */
+int hc_seg_decompress_ranges(const uint8_t *in, uint64_t in_len, const hc_seg_read_t *reads, uint32_t n_reads,
+                             uint8_t *out, uint64_t out_cap, uint64_t *out_len, uint64_t *bad_segment);
+
+/* Host only, no device: the rows of a rectangle as a read list. Of a raw buffer of raw_len bytes read
+ * as rows of `pitch` bytes, row r of the w x h rectangle at column x, row y is bytes
+ * [(y + r) pitch + x, + w), and goes to dst_off r w: reads[r], h entries, sorted. HC_ERR_ARG for a null
+ * `reads` with h > 0, pitch == 0, x + w > pitch, any product or sum that wraps, and, when w and h are
+ * not 0, (y + h - 1) pitch + x + w > raw_len; HC_OK otherwise. w == 0 gives h empty reads (which the
+ * read calls still hold to offset <= raw_len). */
+int hc_seg_rect_reads(uint64_t raw_len, uint64_t pitch, uint64_t x, uint64_t y, uint64_t w, uint64_t h,
+                      hc_seg_read_t *reads /* h entries */);
+
+/* ---------------------------------------------------------------------------------------
  * Append: the container of X followed by T from the container of X, without recoding the rest. The cuts are
  * a function of raw_len, seg_bytes, flags and width, every segment restarts the coder's model and
  * segment k is the stream hc_compress writes for its cut alone: so when bytes are appended, every
